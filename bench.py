@@ -14,11 +14,17 @@ itself (torch.distributed.run as a child process, before any GPU call); under to
 Chains never communicate, so there is no collective in the timed path (timing uses a barrier and a MAX
 all-reduce of the elapsed time only); noise is keyed by the GLOBAL chain index (damc.dist.block_plan):
   --scaling strong (default): the global B=128 (and 2B prior) chains split over the ranks (BASELINE.md's
-                    primary curve), "scaling": "strong"; the JSON records the per-rank batch.  For N > 1 a
-                    weak-scaling pass (B=128 chains per rank) is timed after it and reported as "weak_scaling".
+                    primary curve), "scaling": "strong"; the JSON records the per-rank batch.  With --full and
+                    N > 1 a weak-scaling pass (B=128 chains per rank) is timed after it and reported as "weak_scaling".
   --scaling weak:   B=128 chains per rank -> per-GPU work fixed, "scaling": "weak".
 
-Data: synthetic (counter-hash weights / x ~ U[-1,1] / z0 ~ N(0,1); no datasets offline).
+Data: synthetic (counter-hash weights / x ~ U[-1,1] / z0 ~ N(0,1); no datasets offline).  The same arguments give the
+same inputs and noise seeds in every run.
+
+A plain run sets up, warms up, times --steps blocks, writes the last block's chains (--dump-outputs DIR) and prints
+the headline line.  --full adds everything else to the line, each from runs of its own after the timed ones: the
+per-class kernel times and roofline (live HIP events around the dominant classes inside the timed region, too), the
+weak-scaling pass (N > 1), the per-leg / amortizer / G- and Q-update / other-config timings and the CPU baseline.
 """
 import argparse
 import json
@@ -482,6 +488,51 @@ def upconv_dgrad_algorithmic_bytes(bsz):
     return tot / len(UPCONV_FWD_LAYERS)
 
 
+def dump_outputs(dirname, rank, world, zbuf, pbuf):
+    """--dump-outputs: this rank's chains after the last timed block, what a caller of the block receives: the posterior
+    chains z and the prior chains p, float32, as DIR/posterior_z.npy and DIR/prior_z.npy (N > 1: ..._rank<r>.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(dirname, "posterior_z%s.npy" % sfx), zbuf.cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(dirname, "prior_z%s.npy" % sfx), pbuf.cpu().numpy().astype(np.float32, copy=False))
+
+
+def headline(args, world, plan, t_max, limb):
+    """The result line of a plain run: what the timed blocks alone give (t_max: their wall time, max over ranks)."""
+    chains = world * B if args.scaling == "weak" else B
+    post_flops_step = 4.0 * B * 1089.2e6  # SURVEY.md §8(d): 4 * B * MAC_G per posterior step
+    return {
+        "metric": "Langevin z-steps/sec (B=128, z_dim=128, CIFAR-10)",
+        "value": round(chains * POST_STEPS * args.steps / t_max, 2),
+        "unit": "z-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * t_max / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (counter-hash weights, x~U[-1,1], z0~N(0,1); CIFAR-10 _netG_cifar10 ngf=128 + _netE)",
+        "config": {
+            "workload": "cifar10 train-iteration Langevin block: 30 posterior steps on B=128 + 60 prior "
+                        "steps on 2B=256 %s (value counts posterior z-steps only)"
+                        % ("per rank" if args.scaling == "weak" else "split over the ranks"),
+            "global_batch": chains, "per_rank_batch": plan["post_count"],
+            "per_rank_prior_chains": plan["prior_count"], "z_dim": NZ, "ngf": NGF, "posterior_steps": POST_STEPS,
+            "prior_steps": PRIOR_STEPS, "sigma": SIGMA, "step_size": S_POST, "prior_step_size": S_PRIOR,
+            "parallelism": "dp%d (chains sharded, no collective)" % world,
+        },
+        "gemm_arith": ("fp32 operands as 3 bf16 limbs, 6 limb products per fp32 product on "
+                       "v_mfma_f32_16x16x32_bf16, fp32 accumulation; error vs fp64 equal to the fp32-MFMA "
+                       "engine's (profiles/r01/gemm_bench.txt)") if limb
+                      else "fp32 v_mfma_f32_32x32x2_f32 (exact fp32 fmaf chains)",
+        "posterior_tflops_effective": round(post_flops_step * POST_STEPS * args.steps / t_max / 1e12, 2),
+        "batch_iterations_per_s": round(args.steps / t_max, 3),
+        "cpu_baseline": None,
+    }
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` outside a launcher: run N ranks under torch.distributed.run as a CHILD process (this
     process has not touched the GPU, and is never replaced by exec) and return its exit code.  Rank 0 prints the
@@ -523,6 +574,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="strong (default): the global B=128 split over the ranks; weak: B=128 chains per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the chains of the last timed step as DIR/posterior_z.npy and DIR/prior_z.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and report the kernel classes and roofline, the "
+                         "weak-scaling pass, the per-leg / amortizer / update / other-config timings and the CPU "
+                         "baseline (the --no-* and --cpu-* options below trim it)")
     ap.add_argument("--no-weak-extra", action="store_true", help="N > 1: skip the weak-scaling pass after the timed one")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
@@ -604,7 +661,7 @@ def main():
     L.damc_prof_reset()
     # live HIP events only around the dominant kernel classes (every event pair costs the stream a gap)
     L.damc_prof_select(b"upconv_fwd,upconv_dgrad")
-    L.damc_prof_enable(0 if args.no_live_prof else 1)
+    L.damc_prof_enable(1 if args.full and not args.no_live_prof else 0)
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -617,6 +674,15 @@ def main():
     dump = os.environ.get("DAMC_BENCH_DUMP")
     if dump:  # tests only: this rank's chains after its last block, with its slice of the global batch
         torch.save({"z": zbuf.cpu(), "p": pbuf.cpu(), "plan": dict(plan)}, os.path.join(dump, "rank%d.pt" % rank))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, zbuf, pbuf)
+    if not args.full:
+        t_max = max_over_ranks(elapsed)
+        if rank == 0:
+            print(json.dumps(headline(args, world, plan, t_max, limb)))
+        if dist:
+            tdist.destroy_process_group()
+        return 0
 
     # per-class kernel time from the live HIP events
     import ctypes
@@ -692,9 +758,6 @@ def main():
         legs = config_legs(lv, device, limb_peak)
 
     if rank == 0:
-        chains = world * B if args.scaling == "weak" else B
-        zsteps = chains * POST_STEPS * args.steps
-        value = zsteps / t_max
         c = classes.get(dom, dict(total_ms=float("nan"), launches=1, flops=float("nan")))
         avg_s = c["total_ms"] / c["launches"] / 1e3
         flops_per_launch = c["flops"] / c["launches"]
@@ -705,29 +768,8 @@ def main():
             plan["post_count"])
         gemm_ms = sum(breakdown[k]["total_ms"] for k in breakdown if k.startswith(("upconv", "proj"))) or None
         gemm_fl = sum(breakdown[k]["flops"] for k in breakdown if k.startswith(("upconv", "proj")))
-        post_flops_step = 4.0 * B * 1089.2e6  # 4 * B * MAC_G per posterior step
-        out = {
-            "metric": "Langevin z-steps/sec (B=128, z_dim=128, CIFAR-10)",
-            "value": round(value, 2),
-            "unit": "z-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * t_max / args.steps, 3),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (counter-hash weights, x~U[-1,1], z0~N(0,1); CIFAR-10 _netG_cifar10 ngf=128 + _netE)",
-            "config": {
-                "workload": "cifar10 train-iteration Langevin block: 30 posterior steps on B=128 + 60 prior "
-                            "steps on 2B=256 %s (value counts posterior z-steps only)"
-                            % ("per rank" if args.scaling == "weak" else "split over the ranks"),
-                "global_batch": chains, "per_rank_batch": plan["post_count"],
-                "per_rank_prior_chains": plan["prior_count"], "z_dim": NZ, "ngf": NGF, "posterior_steps": POST_STEPS,
-                "prior_steps": PRIOR_STEPS, "sigma": SIGMA, "step_size": S_POST, "prior_step_size": S_PRIOR,
-                "parallelism": "dp%d (chains sharded, no collective)" % world,
-            },
+        out = headline(args, world, plan, t_max, limb)
+        out.update({
             "roofline": {
                 "bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": round(peak, 1),
                 "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
@@ -749,20 +791,13 @@ def main():
                                                                        achieved * LIMB_PRODUCTS)) if limb
                               else "fp32 MFMA dense peak",
             },
-            "gemm_arith": ("fp32 operands as 3 bf16 limbs, 6 limb products per fp32 product on "
-                           "v_mfma_f32_16x16x32_bf16, fp32 accumulation; error vs fp64 equal to the fp32-MFMA "
-                           "engine's (profiles/r01/gemm_bench.txt)") if limb
-                          else "fp32 v_mfma_f32_32x32x2_f32 (exact fp32 fmaf chains)",
-            "posterior_tflops_effective": round(post_flops_step * POST_STEPS * args.steps / t_max / 1e12, 2),
             "gemm_classes_tflops": round(gemm_fl / (gemm_ms / 1e3) / 1e12, 2) if gemm_ms else None,
             "kernel_classes": {k: dict(avg_ms=round(v["total_ms"] / v["launches"], 4), launches=v["launches"])
                                for k, v in breakdown.items()},
             "prior_us_per_step": round(1e3 * breakdown["prior_chain"]["total_ms"]
                                        / breakdown["prior_chain"]["launches"] / PRIOR_STEPS, 2)
             if "prior_chain" in breakdown else None,
-            "batch_iterations_per_s": round(args.steps / t_max, 3),
-            "cpu_baseline": None,
-        }
+        })
         if dist:
             out["per_rank"] = {"dominant_class": dom, "avg_launch_ms_max_over_ranks": round(dom_avg_ms_max, 4),
                                "backend": backend}
@@ -778,7 +813,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.cpu_budget, full=args.cpu_full)
             out["cpu_baseline"] = cb
-            out["speedup_vs_cpu"] = round(value / cb["value"], 1)
+            out["speedup_vs_cpu"] = round(out["value"] / cb["value"], 1)
         print(json.dumps(out))
     if dist:
         tdist.destroy_process_group()

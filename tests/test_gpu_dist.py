@@ -24,13 +24,16 @@ def _port():
         return s.getsockname()[1]
 
 
-def _run(tmp, world, scaling, torchrun=False, backend="gloo", extra_args=(), timeout=240, **extra_env):
+def _run(tmp, world, scaling, torchrun=False, backend="gloo", extra_args=(), timeout=240, full=False, **extra_env):
+    """One bench run; full: with --full (trimmed to the kernel classes, the roofline and the weak-scaling pass)."""
     os.makedirs(tmp, exist_ok=True)
     env = dict(os.environ, DAMC_DIST_BACKEND=backend, DAMC_BENCH_DUMP=str(tmp), **extra_env)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    args = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
-            "--scaling", scaling] + list(extra_args)
+    args = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--scaling", scaling]
+    if full:
+        args += ["--full", "--no-extras", "--no-cpu-baseline"]
+    args += list(extra_args)
     if torchrun:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", str(world),
                "--master-addr", "127.0.0.1", "--master-port", str(_port())] + args
@@ -47,7 +50,7 @@ def test_two_ranks_strong_scaling_union_is_the_one_rank_block(tmp_path, gpu_devi
     one.mkdir()
     two.mkdir()
     j1 = _run(one, 1, "strong")
-    j2 = _run(two, 2, "strong")
+    j2 = _run(two, 2, "strong", full=True)
     assert j2["n_gpus"] == 2 and j2["scaling"] == "strong"
     assert j2["config"]["global_batch"] == 128 and j2["config"]["per_rank_batch"] == 64
     assert j2["weak_scaling"]["per_rank_batch"] == 128 and j2["weak_scaling"]["global_batch"] == 256
@@ -87,6 +90,23 @@ def test_two_ranks_weak_scaling_line(tmp_path, gpu_device):
     assert [p["plan"]["post_start"] for p in parts] == [0, 128]
     # distinct global chains: the two ranks' noise streams differ, so their chains do too
     assert not torch.equal(parts[0]["z"], parts[1]["z"])
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_steps_chains(tmp_path, gpu_device):
+    """A plain run (no --full) prints the headline fields only, and --dump-outputs DIR writes the chains of the last
+    timed step as float32 .npy files: the arrays the DAMC_BENCH_DUMP record of the same run holds."""
+    import numpy as np
+
+    j = _run(tmp_path, 1, "strong", extra_args=["--dump-outputs", str(tmp_path / "out")])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert abs(j["value"] - 128 * 30 / (j["ms_per_step"] / 1e3)) <= 1e-3 * j["value"]
+    assert (j["unit"], j["dtype"], j["higher_is_better"]) == ("z-steps/s", "f32", True)
+    assert not {"roofline", "kernel_classes", "langevin_legs", "config_legs", "speedup_vs_cpu"} & set(j)
+    ref = torch.load(tmp_path / "rank0.pt", weights_only=True)
+    z, p = np.load(tmp_path / "out" / "posterior_z.npy"), np.load(tmp_path / "out" / "prior_z.npy")
+    assert z.dtype == np.float32 and p.dtype == np.float32
+    assert z.shape == (128, 128) and p.shape == (256, 128)
+    assert np.array_equal(z, ref["z"].numpy()) and np.array_equal(p, ref["p"].numpy())
 
 
 def test_one_rank_over_rccl_is_the_plain_block(tmp_path, gpu_device):

@@ -10,4 +10,4 @@ for b in 0 1; do
   timeout -k 10 120 python3 tools/b16_profile.py 8 2>&1 | grep "per posterior" || exit 1
   timeout -k 10 120 python3 tools/b16_profile.py 32 2>&1 | grep "per posterior" || exit 1
 done
-timeout -k 10 300 python3 bench.py > gpurun_out/bpw_bench.json 2> gpurun_out/bpw_bench.err && cat gpurun_out/bpw_bench.json
+timeout -k 10 600 python3 bench.py --full
