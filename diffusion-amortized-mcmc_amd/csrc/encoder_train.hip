@@ -294,6 +294,7 @@ int backward_up(const float* x, const float* dy, const float* w, int B, int hin,
     a.B3 = reinterpret_cast<const unsigned short*>(t.wf + n);
     a.b_negblk = 1;  // damc_pack_generator_layer's x3 copy (up_view(...)'s forward sign block: generator.hip up2_negk_fwd)
     a.negk = x3_conv_negk((long)ho * wo, cin, 4 * cout, 4);
+    a.kwalk = x3_up2_walk(cout);  // that copy's K order (the view's forward gathers cout channels)
   }
   return launch_gemm(a, A_CONV, EPI_BIAS_ACT, O_PHASE, 4, "enc_dgrad", 2.0 * M * cout * cin * 16, s);
 }

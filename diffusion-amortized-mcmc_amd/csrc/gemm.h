@@ -124,10 +124,14 @@ struct GemmArgs {
   unsigned* kepoch_ctr = nullptr;
   unsigned kepoch = 0;
   unsigned* fixup_probe = nullptr;  // damc_x3_fixup_probe's counters (diagnostics; null: off)
-  // limb engine, A_CONV (not O_WGRAD): 1 = the K walk of a 4 x 4 conv is channel-slice-major with parity-grouped taps
-  // (x3_walk_tap): K tile kt = 32 channels 32 (kt / 16) .. of tap x3_walk_tap(kt % 16), and the weight operand is
-  // packed in that order (x3_conv_walk); 0 = tap-major
+  // limb engine, A_CONV (not O_WGRAD): 1 = the K walk is channel-slice-major.  O_DENSE (a 4 x 4 conv): parity-grouped
+  // taps (x3_walk_tap), K tile kt = 32 channels 32 (kt / 16) .. of tap x3_walk_tap(kt % 16).  O_PHASE (a phase's 2 x 2
+  // conv): K tile kt = 32 channels 32 (kt / 4) .. of tap kt % 4.  The weight operand is packed in that order
+  // (x3_conv_walk for the encoder's convs, x3_up2_walk for the generator's k4 s2 layers); 0 = tap-major
   int kwalk = 0;
+  // limb engine, F32A with kwalk (round 7): 1 = the launcher may stage one fp32 input image per group of four K tiles
+  // (gemm.hip X3_TAPSHARE) where the geometry allows it (x3_tapshare_ok); bitwise the per-tap staging
+  int tapshare = 0;
   // InstanceNorm statistics of the epilogue result (round 6; limb engine, O_DENSE, EPI_BIAS_ACT, unsplit 256 x 128
   // tiles: the encoder's norms): per (sample, 256-row strip, channel) {n, mean, m2} at
   // in_part[((b * N + n) * in_S + strip) * 3] (in_stats_kernel's layout, in_merge_kernel reads it), computed by
@@ -231,6 +235,21 @@ inline int x3_conv_negk(long m_per_sample, int N, int K, int zdim) {
   }
   while (nk > 256 && K % nk != 0) nk >>= 1;
   return nk;
+}
+// K order of the limb copies of a generator k4 s2 p1 ConvT layer (round 7), from the layer's shape alone like the sign
+// block: slice-major whenever the gathered channel count is whole 32-channel slices (every layer the limb engine
+// takes).  cg = the forward's cin (rows of 4 cin per phase: [c / 32][tap][c % 32], launch_split_x3_cmaj's order) or
+// the input gradient's cout (rows of 16 cout: the x3_conv_walk order).  The four K tiles of a group (slice, parity
+// class) then read one input image displaced by 0 / 1 grid positions, which the F32A loop stages once (gemm.hip
+// X3_TAPSHARE).  Every packer and every launch of a call reads this rule; the fp32 copies keep their layout
+inline int x3_up2_walk(int cg) { return (cg > 0 && cg % 32 == 0) ? 1 : 0; }
+// whether a slice-major F32A launch on an Hq x Wq output grid stages one image per group: a 256-row M tile must hold
+// whole images (so a displaced row is in the tile or a padding pixel), and the 64-row DMA pieces must be a uniform
+// pixel stride apart (whole images, or whole grid rows of one image)
+inline int x3_tapshare_ok(int hq, int wq) {
+  const int hw = hq * wq;
+  if (hq <= 0 || wq <= 0 || 256 % hw != 0) return 0;
+  return (64 % hw == 0 || (hw % 64 == 0 && 64 % wq == 0)) ? 1 : 0;
 }
 // the fused output-layer projection as a kernel of its own: P[pix][n] = sum_c h[pix][c] w[n][c] (c < C <= 256,
 // C % 16 == 0; n < np, np = 32 or 64; w rows ldw floats), bitwise the fused form (same MFMA sequence per row); for

@@ -13,6 +13,7 @@
 // Config (BK, OCC, MT): K-tile depth, workgroups per CU for the launch bounds, MFMA tiles per wave
 // along M.  tools/gemm_bench.hip A/B-tests them on the generator's convolutions.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -1070,9 +1071,21 @@ constexpr int X3_NARROW = 4194304;
 // split-K with the in-GEMM ordered fix-up (GemmArgs::kticket; the F32A register-slab path): the last workgroup of a
 // tile to arrive sums the tile's slabs in slab order and runs the unsplit epilogue, so no reduce launch follows
 constexpr int X3_FIXUP = 8388608;
+// X3_TAPSHARE (round 7; F32A with the slice-major walk GemmArgs::kwalk, an Hq x Wq grid that x3_tapshare_ok accepts):
+// the four K tiles of a group (one 32-channel slice x the four taps of a ConvT phase, or of a parity class of the
+// stride-2 4 x 4 conv) read the same 256 input pixels displaced by 0 / +-1 grid positions, so the undisplaced 256 x
+// 128-B fp32 image is staged once per group (one 64-row DMA piece per K tile, two image buffers) and each tap's
+// fragment read takes LDS row r + delta(tap), or a 128-B all-zero row where the tap falls in the padding: 8 KB instead
+// of 32 KB of A per K tile, the same fp32 operands, bitwise the per-tap staging
+constexpr int X3_TAPSHARE = 16777216;
 constexpr int X3_FIXUP_WAIT = 3000;  // the fix-up's bounded wait for the other slices: 30 us of s_memrealtime (100 MHz)
 static unsigned* g_fixup_probe = nullptr;  // damc_x3_fixup_probe (diagnostics)
 __device__ __forceinline__ int f32a_swz(int r) { return ((r >> 1) & 7) ^ ((((r >> 2) ^ (r >> 3)) & 1) << 1); }
+// the swizzle of the X3_TAPSHARE image: a tap's fragment read takes rows r + delta, so the 16 rows of a ds_read_b128
+// lane group arrive rotated by any delta mod 16, where f32a_swz is 2-way for every rotation but 0 and 8.  With row bit
+// 1 -> chunk bit 0 and row bit 2 -> chunk bit 2 (the bank group of a 16-B chunk is 8 (row & 1) + chunk) every rotation
+// of every lane group hits 16 distinct bank groups
+__device__ __forceinline__ int ts_swz(int r) { return ((r >> 1) & 1) | (((r >> 2) & 1) << 2); }
 static_assert(X3_NEGK % 32 == 0 && (X3_NEGK & (X3_NEGK - 1)) == 0, "sign blocks are whole K tiles, a power of two");
 constexpr int X3_CHUNKS = 12;  // 16-B chunks per row and K tile (4 octets x 3 limbs)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -1213,7 +1226,8 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
                 "F32A: the default 16x16-tile LDS-DMA path (A/B builds: + the channel-major walk 8, the raster 16)");
   constexpr int AROWB = F32A ? X3A_ROWB : X3_ROWB, ESZ = F32A ? 4 : 6;
   constexpr int AJ = (BM * (F32A ? 8 : X3_CHUNKS) + 511) / 512, BJ = BN * X3_CHUNKS / 512;  // NARROW: 1.5 -> 2
-  constexpr int BUFB = BM * AROWB + BN * X3_ROWB;  // one LDS buffer (A image, then B image)
+  // one LDS buffer (A image, then B image; X3_TAPSHARE: then two all-zero 128-B rows)
+  constexpr int BUFB = BM * AROWB + BN * X3_ROWB + ((V & X3_TAPSHARE) ? 2 * X3A_ROWB : 0);
   // K tiles per MFMA accumulation block = the GEMM's sign block (GemmArgs::negk, a power of two >= 32); 64: A/B of
   // the block length (no b_negblk)
   const int FLOG = __builtin_ctz((unsigned)p.negk >> 5) + ((V & 64) ? 2 : 0), FLUSH = 1 << FLOG;
@@ -1256,6 +1270,8 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   // in-GEMM ordered fix-up of the split-K slabs (round 6; the protocol is described where the epilogue runs it)
   constexpr bool FIXUP = (V & X3_FIXUP) != 0;
   static_assert(!FIXUP || (KREG && F32A), "FIXUP: the F32A register-slab split-K path");
+  constexpr bool TSHARE = (V & X3_TAPSHARE) != 0;
+  static_assert(!TSHARE || (F32A && OM != O_WGRAD && !(V & 8)), "TAPSHARE: the F32A path on the slice-major walk");
   const int nslz = KSPLIT ? p.ksplit / p.kbpw : 1;
   const int zph = KSPLIT ? z / nslz : z, zsl = KSPLIT ? z - zph * nslz : 0;
   if (OM == O_PHASE) {
@@ -1347,16 +1363,17 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   }
 
   int tap = 0, ci0 = 0, tky = 0, tkx = 0;
-  // GemmArgs::kwalk (a 4 x 4 conv, the default / F32A LDS-DMA paths): K tile kt = channels 32 (kt / 16) .. of tap
-  // x3_walk_tap(kt % 16); wpos = kt % 16
-  const bool walk = OM == O_DENSE && p.kwalk != 0;  // (the encoder's convs; compile-time off for the ConvT phases)
+  // GemmArgs::kwalk: K tile kt = channels 32 (kt / WT) .. of the tap at walk position wpos = kt % WT; O_DENSE (a
+  // 4 x 4 conv): WT = 16, tap x3_walk_tap(wpos); O_PHASE (a phase's 2 x 2 conv): WT = 4, tap wpos
+  const bool walk = OM != O_WGRAD && p.kwalk != 0;
+  constexpr int WT = OM == O_PHASE ? 4 : 16;
   int wpos = 0;
   if (OM != O_WGRAD && kbeg > 0) {  // a split slice starts mid-walk
     if (walk) {
       const int kt = kbeg / X3_BK;
-      wpos = kt & 15;
-      ci0 = (kt >> 4) * X3_BK;
-      tap = x3_walk_tap(wpos);
+      wpos = kt & (WT - 1);
+      ci0 = (kt / WT) * X3_BK;
+      tap = OM == O_PHASE ? wpos : x3_walk_tap(wpos);
     } else {  // tap-major: K tile = (tap, 32 channels)
       tap = kbeg / Cg;
       ci0 = kbeg - tap * Cg;
@@ -1374,13 +1391,13 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   // the next K tile's (channels, tap): tap-major, or the 4 x 4 conv walk
   auto next_ktile = [&]() {
     if (walk) {
-      if (++wpos == 16) {
+      if (++wpos == WT) {
         wpos = 0;
         ci0 += X3_BK;
       }
-      tap = x3_walk_tap(wpos);
-      tky = tap >> 2;
-      tkx = tap & 3;
+      tap = OM == O_PHASE ? wpos : x3_walk_tap(wpos);
+      tky = OM == O_PHASE ? tap >> 1 : tap >> 2;
+      tkx = OM == O_PHASE ? tap & 1 : tap & 3;
       set_tap();
       return;
     }
@@ -1578,16 +1595,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
       for (int j = 0; j < BJ; ++j)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_t)(base + BM * X3_ROWB + 512 * 16 * j), 16, (int)boff[j],
                                                  k0 * 6, 0, 0);
-      ci0 += X3_BK;
-      if (ci0 == Cg) {
-        ci0 = 0;
-        ++tap;
-        if (++tkx == kw) {
-          tkx = 0;
-          ++tky;
-        }
-        set_tap();
-      }
+      next_ktile();
     };
     if (nk > 0) dma_n(kbeg, 0);
     __syncthreads();
@@ -1681,23 +1689,124 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
 #pragma unroll
         for (int e = 0; e < 8; e += 2) split2(av, f, a, e);
     };
-    bf16x8 fx[2][3], fy[2][3], fb[2][3];
-    if (nk > 0) {
-      dma_a(0);
-      dma_b(kbeg, 0);
+    // ---- X3_TAPSHARE: one image per group of four K tiles.  The launcher guarantees the slice-major walk, whole groups
+    // per workgroup (K slices start at multiples of 4 K tiles), hwq | 256 with 64-row pieces a uniform stride apart
+    // (x3_tapshare_ok), and the geometry of a ConvT phase (2 x 2, stride 1) or of its input gradient (4 x 4, stride 2,
+    // pad 1).  Image of local group G in the A half of buffer G & 1; piece j = rows 64 j .. 64 j + 63 (chunk id tid +
+    // 512 j).  DMA: this thread's chunk of the undisplaced pixel of row tid >> 3, pieces ts_pstr bytes apart, rows
+    // beyond M out of range.
+    // Behind each buffer's B image, two all-zero rows (one per row parity, ZREL): a padding tap reads the chunk it
+    // would read in a live row of its parity, so it takes that row's bank group and the lane group stays conflict-free.
+    // Behind the buffers, the read table (TOFF): for walk position pos and tile row r, the byte offset inside a buffer
+    // of the row tap(pos) reads for r -- image row r + delta(pos) with that row's swizzle applied to chunk 0, or the
+    // zero row -- built once per workgroup, so a tile's read addresses cost two ds_read_b32 and two VALU per lane
+    // instead of the mask test, the displacement and the swizzle (~30 VALU that found no MFMA gap)
+    constexpr int ZREL = BM * AROWB + BN * X3_ROWB, TOFF = 2 * BUFB, NT = OM == O_PHASE ? 4 : 16;
+    static_assert(!TSHARE || TOFF + NT * BM * 4 <= 2 * (BM + BN) * X3_ROWB, "no room for the read table");
+    unsigned ts_ibase = 0;
+    int ts_nv = 0, ts_pstr = 0, ts_o[2] = {0, 0};
+    if constexpr (TSHARE) {
+      const int r0 = tid >> 3, mi = m0 + r0;
+      const unsigned b = mi / hwq, r = mi - b * hwq, qy = r / p.Wq, qx = r - qy * p.Wq;
+      ts_ibase = ((b * p.Hin + qy * p.stride) * Win + qx * p.stride) * Cg * 4 + ((tid & 7) ^ ts_swz(r0)) * 16;
+      ts_nv = min(4, max(0, (p.M - mi + 63) >> 6));
+      ts_pstr = ((64 % hwq == 0) ? (64 / hwq) * p.Hin * Win : (64 / p.Wq) * p.stride * Win) * Cg * 4;
+      for (int id = tid; id < NT * BM; id += 512) {
+        const int row = id & (BM - 1), pos = id >> 8, m = m0 + row;
+        int ky, kx, dlt;
+        if constexpr (OM == O_PHASE) {
+          ky = pos >> 1;
+          kx = pos & 1;
+          dlt = (ky - pad_y) * p.Wq + kx - pad_x;
+        } else {
+          const int c = pos >> 2, jj = pos & 3, tp = x3_walk_tap(pos);
+          ky = tp >> 2;
+          kx = tp & 3;
+          dlt = ((jj >> 1) - 1 + (c >> 1)) * p.Wq + (jj & 1) - 1 + (c & 1);
+        }
+        const int bb = m / hwq, rr = m - bb * hwq, y = rr / p.Wq, x = rr - y * p.Wq;
+        const int R = row + dlt;
+        const bool live = m < p.M && (unsigned)(y * p.stride - pad_y + ky) < (unsigned)p.Hin &&
+                          (unsigned)(x * p.stride - pad_x + kx) < (unsigned)Win && (unsigned)R < (unsigned)BM;
+        reinterpret_cast<int*>(smem + TOFF)[id] = (live ? R * X3A_ROWB : ZREL + (R & 1) * X3A_ROWB) + ts_swz(R) * 16;
+      }
+      if (tid < 128) reinterpret_cast<float*>(smem + (tid >> 6) * BUFB + ZREL)[tid & 63] = 0.f;
     }
-    if (nk > 1) dma_a(1);
-    __syncthreads();
-    rd_split(smem, fx);
+    // piece j of local group G: global group gg = (slice, class) for the 4 x 4 conv (class c = taps of parity (c >> 1,
+    // c & 1), reading the pixels of the opposite parity), slice for a ConvT phase
+    auto dma_img = [&](int G, int j) {
+      const int gg = (kt0 >> 2) + G;
+      int sl = gg, coff = 0;
+      if constexpr (OM == O_DENSE) {
+        const int c = gg & 3;
+        sl = gg >> 2;
+        coff = ((1 - (c >> 1)) * Win + (1 - (c & 1))) * Cg * 4;
+      }
+      unsigned char* dst = smem + (G & 1) * BUFB + wbase + 512 * 16 * j;
+      const int vo = j < ts_nv ? (int)(ts_ibase + (unsigned)(j * ts_pstr)) : (int)KM_OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)dst, 16, vo, sl * (X3_BK * 4) + coff, 0, 0);
+    };
+    // ts_o: the LDS byte addresses of this lane's two fragment rows (chunk 2 loct; chunk 2 loct + 1 is at ^ 16) of
+    // local K tile ktn, from the table; every address is an image row or a zero row of the tile's buffer
+    const int ts_tb = TOFF + (wave * 32 + lrow) * 4;
+    auto ts_addr = [&](int ktn) {
+      const int ta = ts_tb + ((kt0 + ktn) & (NT - 1)) * (BM * 4), ib = ((ktn >> 2) & 1) * BUFB;
+#pragma unroll
+      for (int a = 0; a < 2; ++a) ts_o[a] = (*reinterpret_cast<const int*>(smem + ta + a * 64) ^ (loct << 5)) + ib;
+    };
+    auto rd_a_ts = [&](f32x4 (&av)[2][2]) {
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        av[a][0] = *reinterpret_cast<const f32x4*>(smem + ts_o[a]);
+        av[a][1] = *reinterpret_cast<const f32x4*>(smem + (ts_o[a] ^ 16));
+      }
+    };
+    bf16x8 fx[2][3], fy[2][3], fb[2][3];
+    if constexpr (TSHARE) {
+      if (nk > 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dma_img(0, j);
+        dma_b(kbeg, 0);
+      }
+      if (nk > 4) dma_img(1, 0);
+      __syncthreads();
+      f32x4 av0[2][2];
+      ts_addr(0);
+      rd_a_ts(av0);
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) split2(av0, fx, a, e);
+      ts_addr(1);
+    } else {
+      if (nk > 0) {
+        dma_a(0);
+        dma_b(kbeg, 0);
+      }
+      if (nk > 1) dma_a(1);
+      __syncthreads();
+      rd_split(smem, fx);
+    }
     constexpr int SG_MFMA = 0x8, SG_VALU = 0x2, SG_DS_RD = 0x100;
     auto tile = [&](int kt, bf16x8 (&fc)[2][3], bf16x8 (&fn)[2][3]) {
       const unsigned char* base = smem + (kt & 1) * BUFB;
       if (kt + 1 < nk) dma_b(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1);
-      if (kt + 2 < nk) dma_a(kt & 1);
+      if constexpr (TSHARE) {
+        // one piece of the next group's image per tile: group G = (kt + 1) / 4 + 1 over tiles 4 G - 5 .. 4 G - 2, into
+        // the buffer whose last read (A(4 G - 5), by tile 4 G - 6) the previous barrier retired; its fourth piece lands
+        // at the barrier of tile 4 G - 2, one tile before A(4 G) is read
+        const int G = ((kt + 1) >> 2) + 1;
+        if (4 * G < nk) dma_img(G, (kt + 1) & 3);
+      } else if (kt + 2 < nk) {
+        dma_a(kt & 1);
+      }
       // A(kt + 1): read and split unconditionally (past the last tile it is stale, in-bounds LDS, never used); two
       // elements per B tile, in that tile's MFMA gaps
       f32x4 av[2][2];
-      rd_a(smem + ((kt + 1) & 1) * BUFB, av);
+      if constexpr (TSHARE)
+        rd_a_ts(av);  // (addresses from the previous tile)
+      else
+        rd_a(smem + ((kt + 1) & 1) * BUFB, av);
       auto rd_b = [&](int t, int slot) {
 #pragma unroll
         for (int l = 0; l < 3; ++l) fb[slot][l] = *reinterpret_cast<const bf16x8*>(base + brow + t * 16 * X3_ROWB + l * 16);
@@ -1706,6 +1815,9 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         if (t + 1 < 8) rd_b(t + 1, (t + 1) & 1);
+        if constexpr (TSHARE) {
+          if (t == 1) ts_addr(kt + 2);  // A(kt + 2)'s read addresses, one tile ahead of their use
+        }
         const int sl = t & 1;
         split2(av, fn, t >> 2, (t & 3) * 2);
 #pragma unroll
@@ -1730,6 +1842,9 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
           __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
         }
         if (t + 2 < 8) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+        if constexpr (TSHARE) {
+          if (t == 0) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 2, 0);  // the two table reads
+        }
       }
       // the next tile's limbs are complete before the barrier: otherwise the compiler sinks the split into the next
       // tile, where it runs ahead of the first MFMAs instead of in this tile's gaps
@@ -2971,8 +3086,32 @@ long x3_ksplit_floats(int M, int N, int K, int zdim, int negk) {  // either bloc
   return ks > 1 ? (long)zdim * ks * std::max((long)M * N, padded) : 0;
 }
 
+// whether an F32A launch stages one image per group of four K tiles (gemm_x3_kernel X3_TAPSHARE): the caller allows it
+// (GemmArgs::tapshare), the walk is slice-major, the conv is a ConvT phase (2 x 2, stride 1) or the stride-2 4 x 4 input
+// gradient, and the grid passes x3_tapshare_ok.  DAMC_X3_TAPSHARE=0 (read per call) keeps the per-tap staging (bitwise
+// the same) for A/B
+static std::atomic<unsigned long long> g_tapshare_launches{0};
+static bool x3_tapshare_shape(const GemmArgs& a, OMode om) {
+  if (!a.a_f32 || !a.kwalk || !x3_tapshare_ok(a.Hq, a.Wq) || a.negk % (4 * X3_BK) != 0) return false;
+  if (om == O_PHASE)
+    return a.kw == 2 && a.stride == 1 && a.Hin == a.Hq && a.Win == a.Wq && a.K == 4 * a.Cg;
+  return om == O_DENSE && a.kw == 4 && a.stride == 2 && a.pad_y == 1 && a.pad_x == 1 && a.Hin == 2 * a.Hq &&
+         a.Win == 2 * a.Wq && a.K == 16 * a.Cg;
+}
+static bool x3_tapshare_on() {
+  const char* e = getenv("DAMC_X3_TAPSHARE");
+  return !(e && e[0] == '0');
+}
+
 template <int EPI, int OM, int V = DAMC_X3_VARIANT>
 static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
+  if constexpr ((V & X3_F32A) != 0 && !(V & (8 | 16 | X3_TAPSHARE)) &&
+                ((EPI == EPI_BIAS_ACT && OM == O_PHASE) || ((EPI == EPI_MASK || EPI == EPI_STORE) && OM == O_DENSE))) {
+    if (a0.tapshare && x3_tapshare_on() && x3_tapshare_shape(a0, (OMode)OM)) {
+      g_tapshare_launches.fetch_add(1, std::memory_order_relaxed);
+      return launch_x3_t<EPI, OM, V | X3_TAPSHARE>(a0, zdim, s);
+    }
+  }
   GemmArgs a = a0;
   constexpr int BM = (V & 524288) ? 128 : X3_BM, BN = (V & 524288) ? 256 : X3_BN;
   const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
@@ -2992,7 +3131,7 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
     // 32 x 32 wave tile reads 2x the LDS fragments per MFMA and stages 1.5x the bytes per flop
     const char* en = getenv("DAMC_X3_NARROW");
     const long nnm = (a.M + 63) / 64;
-    if (a.kslab && !a.proj_out && !a.kwalk && en && en[0] == '1' && (long)ntm * ntn * zdim < 256 &&
+    if (a.kslab && !a.proj_out && en && en[0] == '1' && (long)ntm * ntn * zdim < 256 &&
         nnm * ntn * zdim >= 256) {
       no_stats();
       a.ksplit = 1;
@@ -3019,7 +3158,7 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
       // sign blocks per workgroup: the most (a power of two dividing ks) that still leaves >= 256 workgroups, so one
       // round covers the chip (the default 16x16-tile path only); DAMC_X3_KSPLIT_BPW (read per call) pins it
       int bpw = 1;
-      if ((V & ~X3_F32A) == DAMC_X3_VARIANT && (V & 1) && !(V & (2048 | 65536 | 131072 | 262144))) {
+      if ((V & ~(X3_F32A | X3_TAPSHARE)) == DAMC_X3_VARIANT && (V & 1) && !(V & (2048 | 65536 | 131072 | 262144))) {
         const char* eb = getenv("DAMC_X3_KSPLIT_BPW");
         if (eb) {
           bpw = std::max(1, atoi(eb));
@@ -3038,7 +3177,7 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
       if (!a.kslab_reg) bpw = 1;
       a.kbpw = bpw;
       a.k_per_z = a.K / ks * bpw;
-      if constexpr ((V & ~X3_F32A) == DAMC_X3_VARIANT && OM != O_WGRAD && (V & 1) && (V & 4) &&
+      if constexpr ((V & ~(X3_F32A | X3_TAPSHARE)) == DAMC_X3_VARIANT && OM != O_WGRAD && (V & 1) && (V & 4) &&
                     !(V & (32 | 2048 | 65536 | 131072 | 262144 | 524288))) {
         if constexpr ((V & X3_F32A) != 0 && ((EPI == EPI_BIAS_ACT && OM == O_PHASE) || (EPI == EPI_MASK && OM == O_DENSE))) {
           // round 6, opt-in (DAMC_X3_FIXUP=1, read per call): the in-GEMM ordered fix-up instead of the reduce launch
@@ -3234,8 +3373,9 @@ int launch_split_x3_conv(const float* x, long n, int K, int Cg, unsigned short* 
 // weight W[ci][co][tap] (kk <= 16 taps) read in contiguous rows, written as whole octets of the packed matrix, with
 // its x3 copy (sign-alternating negk blocks, split_x3_negblk_kernel's values) in the same pass -- the per-call
 // packing was scattered 4-byte stores plus a second read for the limb split.
-__device__ __forceinline__ void pack_store_octet(const float (&v)[8], long flat, int k, float* __restrict__ out,
-                                                 unsigned short* __restrict__ x3, int negk) {
+// (flat: fp32 index; the limb octet goes to x3 octet x3_oct, k = its K index within the row in the limb copy's order)
+__device__ __forceinline__ void pack_store_octet(const float (&v)[8], long flat, long x3_oct, int k,
+                                                 float* __restrict__ out, unsigned short* __restrict__ x3, int negk) {
   f32x4* o = reinterpret_cast<f32x4*>(out + flat);
   o[0] = f32x4{v[0], v[1], v[2], v[3]};
   o[1] = f32x4{v[4], v[5], v[6], v[7]};
@@ -3244,7 +3384,7 @@ __device__ __forceinline__ void pack_store_octet(const float (&v)[8], long flat,
     const float u[8] = {sg * v[0], sg * v[1], sg * v[2], sg * v[3], sg * v[4], sg * v[5], sg * v[6], sg * v[7]};
     bf16x8 h, m, l;
     split3_octet(u, h, m, l);
-    bf16x8* y = reinterpret_cast<bf16x8*>(x3) + 3 * (flat / 8);
+    bf16x8* y = reinterpret_cast<bf16x8*>(x3) + 3 * x3_oct;
     y[0] = h;
     y[1] = m;
     y[2] = l;
@@ -3255,7 +3395,7 @@ __device__ __forceinline__ void pack_store_octet(const float (&v)[8], long flat,
 constexpr int PK_ROW_CO = 128;
 __global__ void __launch_bounds__(256) pack_rowT_kernel(const float* __restrict__ w, int cout, int kk,
                                                         float* __restrict__ out, unsigned short* __restrict__ x3,
-                                                        int negk) {
+                                                        int negk, int walk) {
   __shared__ float t[PK_ROW_CO * 65];
   const int ci = blockIdx.y, co0 = blockIdx.x * PK_ROW_CO;
   const int nco = min(PK_ROW_CO, cout - co0), nco8 = nco / 8, ld = kk + 1;
@@ -3267,8 +3407,10 @@ __global__ void __launch_bounds__(256) pack_rowT_kernel(const float* __restrict_
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = t[(c8 * 8 + j) * ld + tap];
-    const int k = tap * cout + co0 + c8 * 8;
-    pack_store_octet(v, (long)ci * kk * cout + k, k, out, x3, negk);
+    const int co = co0 + c8 * 8, k = tap * cout + co;
+    // limb copy in the x3_conv_walk order (walk: the 4 x 4 input gradient, x3_up2_walk): [co / 32][walk pos][co % 32]
+    const int k3 = walk ? (co >> 5) * (16 * 32) + x3_walk_pos(tap) * 32 + (co & 31) : k;
+    pack_store_octet(v, (long)ci * kk * cout + k, ((long)ci * kk * cout + k3) / 8, k3, out, x3, negk);
   }
 }
 
@@ -3277,7 +3419,7 @@ __global__ void __launch_bounds__(256) pack_rowT_kernel(const float* __restrict_
 // input channel's run of 128 contiguous weights).
 __global__ void __launch_bounds__(256) pack_colT_kernel(const float* __restrict__ w, int cin, int cout, int kk, int up2,
                                                         float* __restrict__ out, unsigned short* __restrict__ x3,
-                                                        int negk) {
+                                                        int negk, int walk) {
   __shared__ float t[32 * 129];
   const int cot = 128 / kk, ci0 = blockIdx.x * 32, co0 = blockIdx.y * cot, rl = 128, ld = rl + 1;
   for (int e = threadIdx.x; e < 32 * rl; e += 256) {
@@ -3290,17 +3432,21 @@ __global__ void __launch_bounds__(256) pack_colT_kernel(const float* __restrict_
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = t[(c8 * 8 + j) * ld + r];
-    long seg;
+    long seg, oct3;
     int k = ci0 + c8 * 8;
     if (up2) {  // ky = 3 - py - 2 ty (the stride-2 phase decomposition, generator.hip pack_up2_kernel)
       const int ky = tap >> 2, kx = tap & 3, py = (3 - ky) & 1, px = (3 - kx) & 1;
       const int tt = ((3 - ky - py) >> 1) * 2 + ((3 - kx - px) >> 1);
       seg = ((long)(py * 2 + px) * cout + co) * 4 + tt;
-      k += tt * cin;
+      // limb copy slice-major (walk, x3_up2_walk): the (phase, co) row's 4 cin values as [c / 32][tap][c % 32]
+      // (launch_split_x3_cmaj's order, sw = 32); ci0 is a whole slice
+      k = walk ? (ci0 >> 5) * 128 + tt * 32 + c8 * 8 : k + tt * cin;
+      oct3 = ((seg - tt) * cin + k) / 8;
     } else {
       seg = (long)tap * cout + co;
+      oct3 = (seg * cin + ci0 + c8 * 8) / 8;
     }
-    pack_store_octet(v, seg * cin + ci0 + c8 * 8, k, out, x3, negk);
+    pack_store_octet(v, seg * cin + ci0 + c8 * 8, oct3, k, out, x3, negk);
   }
 }
 
@@ -3313,9 +3459,10 @@ static bool pack_tiled_ok(const void* a, const void* b, const void* c, const voi
 int launch_pack_up2_tiled(const float* w, int cin, int cout, float* wf, unsigned short* wf3, float* wb,
                           unsigned short* wb3, hipStream_t s, int negk_f, int negk_b) {
   if (cin % KM_BK != 0 || cout % KM_BK != 0 || !pack_tiled_ok(wf, wf3, wb, wb3)) return 1;
-  hipLaunchKernelGGL(pack_colT_kernel, dim3(cin / 32, cout / 8), dim3(256), 0, s, w, cin, cout, 16, 1, wf, wf3, negk_f);
+  hipLaunchKernelGGL(pack_colT_kernel, dim3(cin / 32, cout / 8), dim3(256), 0, s, w, cin, cout, 16, 1, wf, wf3, negk_f,
+                     x3_up2_walk(cin));
   hipLaunchKernelGGL(pack_rowT_kernel, dim3((cout + PK_ROW_CO - 1) / PK_ROW_CO, cin), dim3(256), 0, s, w, cout, 16,
-                     wb, wb3, negk_b);
+                     wb, wb3, negk_b, x3_up2_walk(cout));
   return (int)hipGetLastError();
 }
 
@@ -3325,9 +3472,9 @@ int launch_pack_proj_tiled(const float* w, int cin, int cout, int kk, float* wf,
       !pack_tiled_ok(wf, wb, wb3, nullptr))
     return 1;
   hipLaunchKernelGGL(pack_rowT_kernel, dim3((cout + PK_ROW_CO - 1) / PK_ROW_CO, cin), dim3(256), 0, s, w, cout, kk,
-                     wf, (unsigned short*)nullptr, X3_NEGK);
+                     wf, (unsigned short*)nullptr, X3_NEGK, 0);
   hipLaunchKernelGGL(pack_colT_kernel, dim3(cin / 32, cout / (128 / kk)), dim3(256), 0, s, w, cin, cout, kk, 0, wb, wb3,
-                     X3_NEGK);
+                     X3_NEGK, 0);
   return (int)hipGetLastError();
 }
 
@@ -3509,8 +3656,9 @@ static int launch_gemm_x3(const GemmArgs& a, Epi epi, OMode om, int zdim, hipStr
     return DAMC_ERR_ARG;
   if ((om == O_PHASE) != (zdim == 4) || (om == O_DENSE && zdim != 1)) return DAMC_ERR_ARG;
   // the 4 x 4 conv walk (GemmArgs::kwalk): O_DENSE, 16 taps of whole 32-channel slices, the default / F32A tiles only
-  if (a.kwalk && (om != O_DENSE || taps != 16 || a.kw != 4 || a.Cg % 32 != 0 || (DAMC_X3_VARIANT & ~0x105) != 0))
+  if (a.kwalk && (!(om == O_DENSE && taps == 16 && a.kw == 4) && !(om == O_PHASE && taps == 4 && a.kw == 2)))
     return DAMC_ERR_ARG;
+  if (a.kwalk && (a.Cg % 32 != 0 || (DAMC_X3_VARIANT & ~0x105) != 0)) return DAMC_ERR_ARG;
   if (((uintptr_t)a.A3 | (uintptr_t)a.A | (uintptr_t)a.B3 | (uintptr_t)a.C | (uintptr_t)a.C3 | (uintptr_t)a.mask) % 16 !=
       0)
     return DAMC_ERR_ARG;
@@ -3772,6 +3920,10 @@ void set_clock_probe(unsigned long long* buf, int n) {
 extern "C" int damc_clock_probe(unsigned long long* buf, int n_slots) {
   damc::set_clock_probe(buf, n_slots);
   return 0;
+}
+
+extern "C" unsigned long long damc_x3_tapshare_launches(void) {
+  return damc::g_tapshare_launches.load(std::memory_order_relaxed);
 }
 
 extern "C" int damc_x3_fixup_probe(unsigned* buf) {

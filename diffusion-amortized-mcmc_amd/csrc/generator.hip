@@ -1909,6 +1909,8 @@ int forward_hidden(const damc_generator_t* g, const float* z, int B, Workspace& 
         a.B3 = x3_of(L.w_fwd, up2_floats(L));
         a.b_negblk = 1;
         a.negk = up2_negk_fwd(L);
+        a.kwalk = damc::x3_up2_walk(L.cin);  // the limb copy's K order (damc_pack_generator_layer)
+        a.tapshare = 1;
         if (i + 1 < g->n_layers && x3_fwd(g->layers[i + 1])) {  // the next layer's operand
           if (!f32a) a.C3 = ws.h3[i];
           wrote_x3 = true;
@@ -2047,6 +2049,8 @@ int dgrad_layer(const damc_generator_t* g, int B, Workspace& ws, int i, const fl
         a.B3 = x3_of(L.w_bwd, up2_floats(L));
         a.b_negblk = 1;
         a.negk = up2_negk_bwd(L);
+        a.kwalk = damc::x3_up2_walk(L.cout);  // the limb copy's K order (damc_pack_generator_layer)
+        a.tapshare = 1;
         a.kslab = ws.kslab;
         a.kslab_floats = ws.kslab_floats;
         a.kticket = ws.kticket;
@@ -2350,6 +2354,26 @@ extern "C" int damc_x3_layer_sign_block(const damc_layer_t* L, int input_grad) {
   return x3_fwd_cap(*L) ? up2_negk_fwd(*L) : 0;
 }
 
+extern "C" int damc_x3_layer_walk(const damc_layer_t* L, int input_grad) {
+  if (!L) return 0;
+  if (input_grad) return x3_bwd_cap(*L) ? damc::x3_up2_walk(L->cout) : 0;
+  return x3_fwd_cap(*L) ? damc::x3_up2_walk(L->cin) : 0;
+}
+
+extern "C" int damc_x3_walk_ktile(int input_grad, int kt, int* channel0, int* tap) {
+  if (kt < 0) return DAMC_ERR_ARG;
+  const int wt = input_grad ? 16 : 4, pos = kt % wt;
+  if (channel0) *channel0 = (kt / wt) * 32;
+  if (tap) *tap = input_grad ? damc::x3_walk_tap(pos) : pos;
+  return 0;
+}
+
+extern "C" int damc_x3_layer_tapshare(const damc_layer_t* L, int input_grad) {
+  if (!damc_x3_layer_walk(L, input_grad)) return 0;
+  const int nk = input_grad ? up2_negk_bwd(*L) : up2_negk_fwd(*L);
+  return (damc::x3_tapshare_ok(L->hin, L->win) && nk % 128 == 0 && L->hout == 2 * L->hin && L->wout == 2 * L->win) ? 1 : 0;
+}
+
 extern "C" int damc_pack_generator_layer(const damc_layer_t* L, const float* w, float* wf, float* wb, void* stream) {
   if (!L || !w || !wf) return DAMC_ERR_ARG;
   hipStream_t s = as_stream(stream);
@@ -2385,12 +2409,19 @@ extern "C" int damc_pack_generator_layer(const damc_layer_t* L, const float* w, 
       // x3 copies with sign-alternating K blocks (gemm.h GemmArgs::b_negblk): rows of 4 Cin (forward, per phase
       // and output channel) and 16 Cout (input gradient, per input channel)
       // (in the K order the limb-engine kernels walk: damc::launch_split_x3_conv)
+      // (in the slice-major order of damc::x3_up2_walk, which the capability implies)
       if (x3_fwd_cap(*L))
-        DAMC_CHECK((hipError_t)damc::launch_split_x3_conv(wf, n, 4 * L->cin, L->cin, reinterpret_cast<unsigned short*>(wf + n), s,
-                                                          up2_negk_fwd(*L)));
+        DAMC_CHECK((hipError_t)(damc::x3_up2_walk(L->cin)
+                                    ? damc::launch_split_x3_cmaj(wf, n, 4 * L->cin, L->cin, 32,
+                                                                 reinterpret_cast<unsigned short*>(wf + n), s, up2_negk_fwd(*L))
+                                    : damc::launch_split_x3_conv(wf, n, 4 * L->cin, L->cin,
+                                                                 reinterpret_cast<unsigned short*>(wf + n), s, up2_negk_fwd(*L))));
       if (x3_bwd_cap(*L))
-        DAMC_CHECK((hipError_t)damc::launch_split_x3_conv(wb, n, 16 * L->cout, L->cout, reinterpret_cast<unsigned short*>(wb + n), s,
-                                                          up2_negk_bwd(*L)));
+        DAMC_CHECK((hipError_t)(damc::x3_up2_walk(L->cout)
+                                    ? damc::launch_split_x3_walk(wb, n, 16 * L->cout, L->cout,
+                                                                 reinterpret_cast<unsigned short*>(wb + n), s, up2_negk_bwd(*L))
+                                    : damc::launch_split_x3_conv(wb, n, 16 * L->cout, L->cout,
+                                                                 reinterpret_cast<unsigned short*>(wb + n), s, up2_negk_bwd(*L))));
       break;
     case DAMC_LAYER_SMALLC:
       if (wb) DAMC_CHECK(hipMemsetAsync(wb, 0, sizeof(float) * smallc_ntile(*L) * 32 * (size_t)L->cin, s));
@@ -2454,6 +2485,10 @@ extern "C" int damc_likelihood_grad(const damc_generator_t* g, const float* z, c
 
 // ---- per-op hooks for ONE k4 s2 p1 ConvTranspose2d layer (damc_convT_fwd / damc_convT_dgrad),
 // NHWC activations, the same kernels and engine choice as inside the Langevin step
+static bool hook_f32a(const float* act) {
+  const char* fa = getenv("DAMC_X3_F32A");
+  return !(fa && fa[0] == '0') && (uintptr_t)act % 16 == 0;
+}
 static bool up2_hook_ok(const damc_layer_t* L, int B) {
   return L && B > 0 && L->kind == DAMC_LAYER_UP2 && L->k == 4 && L->stride == 2 && L->pad == 1 && L->cin > 0 &&
          L->cout > 0 && L->hout == 2 * L->hin && L->wout == 2 * L->win && L->w_fwd && L->w_bwd;
@@ -2496,12 +2531,20 @@ extern "C" int damc_convT_fwd(const damc_layer_t* L, const float* in, int B, flo
   a.Wout = L->wout;
   int rc;
   if (x3_fwd(*L)) {
-    unsigned short* a3 = reinterpret_cast<unsigned short*>(wsp);
-    if ((rc = damc::launch_split_x3(in, (long)B * L->hin * L->win * L->cin, a3, s))) return rc;
-    a.A3 = a3;
+    // the fp32 input gathered as it is (gemm.hip X3_F32A), as inside the Langevin step; DAMC_X3_F32A=0 (read per call)
+    // gathers a limb copy (bitwise the same)
+    if (hook_f32a(in)) {
+      a.a_f32 = 1;
+    } else {
+      unsigned short* a3 = reinterpret_cast<unsigned short*>(wsp);
+      if ((rc = damc::launch_split_x3(in, (long)B * L->hin * L->win * L->cin, a3, s))) return rc;
+      a.A3 = a3;
+    }
     a.B3 = x3_of(L->w_fwd, up2_floats(*L));
     a.b_negblk = 1;
     a.negk = up2_negk_fwd(*L);
+    a.kwalk = damc::x3_up2_walk(L->cin);
+    a.tapshare = 1;
   }
   return damc::launch_gemm(a, damc::A_CONV, damc::EPI_BIAS_ACT, damc::O_PHASE, 4, "upconv_fwd", conv_flops(*L, B), s);
 }
@@ -2536,12 +2579,18 @@ extern "C" int damc_convT_dgrad(const damc_layer_t* L, const float* gout, int B,
   a.mask_slope = mask_slope;
   int rc;
   if (x3_bwd(*L)) {
-    unsigned short* a3 = reinterpret_cast<unsigned short*>(wsp);
-    if ((rc = damc::launch_split_x3(gout, (long)B * L->hout * L->wout * L->cout, a3, s))) return rc;
-    a.A3 = a3;
+    if (hook_f32a(gout)) {
+      a.a_f32 = 1;
+    } else {
+      unsigned short* a3 = reinterpret_cast<unsigned short*>(wsp);
+      if ((rc = damc::launch_split_x3(gout, (long)B * L->hout * L->wout * L->cout, a3, s))) return rc;
+      a.A3 = a3;
+    }
     a.B3 = x3_of(L->w_bwd, up2_floats(*L));
     a.b_negblk = 1;
     a.negk = up2_negk_bwd(*L);
+    a.kwalk = damc::x3_up2_walk(L->cout);
+    a.tapshare = 1;
   }
   return damc::launch_gemm(a, damc::A_CONV, mask_pre ? damc::EPI_MASK : damc::EPI_STORE, damc::O_DENSE, 1,
                            "upconv_dgrad", conv_flops(*L, B), s);

@@ -193,6 +193,10 @@ _SIGS = {
     "damc_conv2d_x3_bytes": (_SZ, [_I, _I, _I]),
     "damc_x3_sign_block": (_I, []),
     "damc_x3_layer_sign_block": (_I, [ctypes.POINTER(Layer), _I]),
+    "damc_x3_layer_walk": (_I, [ctypes.POINTER(Layer), _I]),
+    "damc_x3_walk_ktile": (_I, [_I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "damc_x3_layer_tapshare": (_I, [ctypes.POINTER(Layer), _I]),
+    "damc_x3_tapshare_launches": (ctypes.c_ulonglong, []),
     "damc_conv2d_x3_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "damc_conv2d_x3_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "damc_clock_probe": (_I, [_P, _I]),

@@ -262,6 +262,21 @@ int damc_x3_conv_walk(int k, int cin);
  * K = 4 Cin) or input gradient (1, K = 16 Cout): 512 or 1024 by the layer's shape alone (gemm.h x3_conv_negk);
  * 0 for a layer without limb weights */
 int damc_x3_layer_sign_block(const damc_layer_t* L, int input_grad);
+/* the K order of those limb weights and of every limb-engine launch that reads them, by the layer's shape alone: 1 =
+ * channel-slice-major (K tile kt of 32 k = channels 32 (kt / 4) .. of the phase's tap kt % 4 in the forward; channels
+ * 32 (kt / 16) .. of the 4 x 4 tap at parity-grouped position kt % 16 in the input gradient), 0 = tap-major or no
+ * limb weights.  The fp32 packings keep their tap-major layout */
+int damc_x3_layer_walk(const damc_layer_t* L, int input_grad);
+/* K tile kt of that walk -> its first channel and its tap (forward: ty * 2 + tx of the phase's 2 x 2 conv; input
+ * gradient: ky * 4 + kx).  Groups of four consecutive K tiles share a channel slice and, in the input gradient, the
+ * taps' (ky, kx) parity */
+int damc_x3_walk_ktile(int input_grad, int kt, int* channel0, int* tap);
+/* 1 when the layer's fp32-gathering limb GEMMs (forward / input gradient) stage one input image per group of four K
+ * tiles (gemm.hip X3_TAPSHARE: the layer walks slice-major and its hin x win grid tiles the 256-row block: hin * win
+ * divides 256); 0: one image per tap, the same bits.  DAMC_X3_TAPSHARE=0 (read per call) forces per-tap staging */
+int damc_x3_layer_tapshare(const damc_layer_t* L, int input_grad);
+/* launches that ran with the shared staging since the library was loaded */
+unsigned long long damc_x3_tapshare_launches(void);
 /* diagnostics: while buf (n_slots * 4 uint64, device memory) is set, every k4 s2 ConvT forward on the limb engine
  * stores, per workgroup w at buf[4 (w % n_slots)], {s_memtime, s_memrealtime} before and after its K loop: the
  * clock the chip holds in that loop is d(memtime) / d(realtime) x 100 MHz.  buf = NULL switches it off.  Not
