@@ -270,13 +270,13 @@ int launch_split_x3(const float* x, long n, unsigned short* y, hipStream_t s);
 // the same for a weight operand whose rows are K long, with the values of the odd X3_NEGK-blocks of each row
 // negated (exact); the GEMM launches that read it set GemmArgs::b_negblk
 int launch_split_x3_negblk(const float* x, long n, int K, unsigned short* y, hipStream_t s, int negk = X3_NEGK);
-// the same reordered for the channel-major K walk: a row's K = taps * Cg values [tap][c] are stored
-// [c / sw][tap][c % sw] (sw channels per slice), sign blocks counted in that order
+// the same reordered for the slice-major K walk (GemmArgs::kwalk; a ConvT phase's forward weights, x3_up2_walk): a
+// row's K = taps * Cg values [tap][c] are stored [c / sw][tap][c % sw] (sw channels per slice), sign blocks counted in
+// that order
 int launch_split_x3_cmaj(const float* x, long n, int K, int Cg, int sw, unsigned short* y, hipStream_t s,
                          int negk = X3_NEGK);
-// the x3 copy of a conv weight (rows of K = taps * Cg) in the order the library's limb-engine kernels walk K:
-// slice-major with sign-alternating blocks when the default variant walks channel-major (DAMC_X3_VARIANT & 8),
-// else tap-major (launch_split_x3_negblk)
+// the x3 copy of a conv weight (rows of K = taps * Cg) in the order the limb engine walks K without GemmArgs::kwalk:
+// tap-major (launch_split_x3_negblk)
 int launch_split_x3_conv(const float* x, long n, int K, int Cg, unsigned short* y, hipStream_t s, int negk = X3_NEGK);
 // the same for a 4 x 4 conv's K-major rows (K = 16 Cg, Cg % 32 == 0) in the x3_conv_walk order
 int launch_split_x3_walk(const float* x, long n, int K, int Cg, unsigned short* y, hipStream_t s, int negk = X3_NEGK);

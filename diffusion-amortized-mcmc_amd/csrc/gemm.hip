@@ -1043,7 +1043,7 @@ static int launch_gemm_km(const GemmArgs& a, Epi epi, OMode om, int zdim, hipStr
 // a1 = bf16(a - a0), a2 = bf16(a - a0 - a1); both subtractions are exact, so the limbs hold all 24
 // significand bits).  A product a*b is the sum of the six limb products with i + j <= 2; the dropped
 // three are below 2^-23 |ab|.  Each limb product is exact in the MFMA (8 x 8 significand bits) and the
-// sum is accumulated in fp32 by v_mfma_f32_32x32x16_bf16, smallest terms first.  Error against fp64 is
+// sum is accumulated in fp32 by v_mfma_f32_16x16x32_bf16, smallest terms first.  Error against fp64 is
 // the fp32 GEMM's (tools/gemm_bench.hip prints both), at 16/6 of the fp32-MFMA rate per clock.
 //
 // "x3" tensor layout: a row of C channels is C/8 octets, each octet stored as [limb][8] bf16 (48 B), so
@@ -1091,15 +1091,21 @@ constexpr int X3_CHUNKS = 12;  // 16-B chunks per row and K tile (4 octets x 3 l
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// V: variant bits (tools/gemm_bench.hip A/B): 256 = fragment reads in MFMA order (below), 1 = v_mfma_f32_16x16x32_bf16 on a 4x4 grid of 16x16 tiles per
-// wave, 2 = s_setprio(1) around the MFMA cluster, 4 = LDS-DMA staging (buffer_load ... lds straight into
-// the lane-linear LDS image, issued one K tile ahead; no staging registers or ds_write), 16 = supertile
-// raster (32 = one MFMA accumulation chain over all of K: no blocking, no sign alternation; A/B only) (a 1-D grid; each XCD's 32 concurrent workgroups form a block of <= 8 M tiles x 4 (N tile, phase) pairs
-// with the 4 phases of an N tile adjacent, so the phases' overlapping input windows and the weight panels are
-// shared in L2 instead of every XCD streaming all phases' panels; DMA and non-WGRAD only)
-#ifndef DAMC_X3_VARIANT
-#define DAMC_X3_VARIANT 261  // measured best (profiles/r02/gemm_bench_rdorder.txt; round 1: 5)
-#endif
+// V, gemm_x3_kernel's variant bits.  The value is part of the kernel's name, which committed profiles and the tools
+// match on, so the bits keep their values.  (The retired experiment bits and what they measured: DESIGN.md.)
+//   X3_BASE      in every instantiation: v_mfma_f32_16x16x32_bf16 on 16x16 tiles (1); LDS-DMA staging (4: buffer_load
+//                ... lds straight into the lane-linear LDS image, one K tile ahead, no staging registers or ds_write);
+//                fragment reads in MFMA order (256).  Measured best, profiles/r02/gemm_bench_rdorder.txt
+//   X3_RASTER    supertile raster (not O_WGRAD): a 1-D grid; each XCD's 32 concurrent workgroups form a block of <= 8
+//                M tiles x 4 (N tile, phase) pairs with the 4 phases of an N tile adjacent, so the phases' overlapping
+//                input windows and the weight panels are shared in L2 instead of every XCD streaming all phases' panels
+//   X3_WIDE      a 128 x 256 block tile (waves 2 along M x 4 along N, each still 64 x 64) instead of 256 x 128: no
+//                half-empty tile at M = 128 (the first layer, M = B) and half the A gather per K tile
+//   X3_KREG      split-K into register-layout slabs (GemmArgs::kslab_reg; launched only split, 256 x 128 tiles): a
+//                compile-time variant, so the block-total registers of the unsplit kernel drop out
+//   X3_F32A, X3_NARROW, X3_FIXUP, X3_TAPSHARE: above
+constexpr int X3_BASE = 261, X3_RASTER = 16, X3_WIDE = 524288, X3_KREG = 1048576;
+constexpr int X3_BITS = X3_BASE | X3_RASTER | X3_WIDE | X3_KREG | X3_F32A | X3_NARROW | X3_FIXUP | X3_TAPSHARE;
 // RNE limb split of 8 consecutive values: v = h + m + l (to 24 significand bits)
 __device__ __forceinline__ void split3_octet(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
 #pragma unroll
@@ -1202,35 +1208,24 @@ int launch_proj_rows(const float* h, long npix, int C, const float* w, int ldw, 
   return (int)hipGetLastError();
 }
 
-template <int EPI, int OM, int V = DAMC_X3_VARIANT>
+template <int EPI, int OM, int V = X3_BASE>
 __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(GemmArgs p) {
-  constexpr bool M16 = (V & 1) != 0;
-  // 262144: 16-deep K stages in a 4-slot LDS ring (three stages in flight across raw barriers, counted vmcnt), each
-  // MFMA taking two limb products over 16 k (P16 main loop below)
-  constexpr bool P16 = (V & 262144) != 0;
-  constexpr bool DMA_OK_P16 = (V & 4) != 0;
-  // 524288: a 128 x 256 block tile (waves 2 along M x 4 along N, each still 64 x 64) instead of 256 x 128: no
-  // half-empty tile at M = 128 (the first layer, M = B) and half the A gather per K tile
-  constexpr bool WIDE = (V & 524288) != 0;
-  static_assert(!(WIDE && P16), "one layout variant at a time");
+  static_assert((V & X3_BASE) == X3_BASE && !(V & ~X3_BITS), "V: X3_BASE and the named variant bits only");
+  constexpr bool WIDE = (V & X3_WIDE) != 0;
   constexpr bool NARROW = (V & X3_NARROW) != 0;
-  static_assert(!NARROW || (!WIDE && !P16 && M16 && (V & 4) && !(V & (8 | 16 | 32 | 64 | 2048 | 1048576 | 2097152))),
-                "NARROW: the default LDS-DMA tap-major path, unsplit");
+  static_assert(!NARROW || !(V & (X3_RASTER | X3_WIDE | X3_KREG | X3_F32A)), "NARROW: the default limb path, unsplit");
   constexpr int BM = WIDE ? 128 : NARROW ? 64 : X3_BM, BN = WIDE ? 256 : X3_BN;
   // X3_F32A: A staged as fp32 (4 B per element instead of 6 B of limbs) and split into its RNE limbs in registers after
   // the fragment read, the same split as the producing epilogue's, so the MFMA operands and results are bitwise the
   // limb path's; waves 8 along M x 1 along N (each 32 x 128), so every A element is split by one wave only
   constexpr bool F32A = (V & X3_F32A) != 0;
-  static_assert(!F32A || (OM != O_WGRAD && M16 && (V & 4) && (V & 256) && !WIDE && !P16 &&
-                          !(V & (32 | 64 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536 | 131072))),
-                "F32A: the default 16x16-tile LDS-DMA path (A/B builds: + the channel-major walk 8, the raster 16)");
+  static_assert(!F32A || (OM != O_WGRAD && !WIDE), "F32A: 256 x 128 tiles, not the weight gradient");
   constexpr int AROWB = F32A ? X3A_ROWB : X3_ROWB, ESZ = F32A ? 4 : 6;
   constexpr int AJ = (BM * (F32A ? 8 : X3_CHUNKS) + 511) / 512, BJ = BN * X3_CHUNKS / 512;  // NARROW: 1.5 -> 2
   // one LDS buffer (A image, then B image; X3_TAPSHARE: then two all-zero 128-B rows)
   constexpr int BUFB = BM * AROWB + BN * X3_ROWB + ((V & X3_TAPSHARE) ? 2 * X3A_ROWB : 0);
-  // K tiles per MFMA accumulation block = the GEMM's sign block (GemmArgs::negk, a power of two >= 32); 64: A/B of
-  // the block length (no b_negblk)
-  const int FLOG = __builtin_ctz((unsigned)p.negk >> 5) + ((V & 64) ? 2 : 0), FLUSH = 1 << FLOG;
+  // K tiles per MFMA accumulation block = the GEMM's sign block (GemmArgs::negk, a power of two >= 32)
+  const int FLOG = __builtin_ctz((unsigned)p.negk >> 5), FLUSH = 1 << FLOG;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (BM + BN) * X3_ROWB];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1241,7 +1236,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     clk_t0 = __builtin_amdgcn_s_memtime();
     clk_r0 = __builtin_amdgcn_s_memrealtime();
   }
-  constexpr bool RASTER = (V & 16) != 0 && OM != O_WGRAD;
+  constexpr bool RASTER = (V & X3_RASTER) != 0 && OM != O_WGRAD;
   const int wgid = xcd_remap(blockIdx.x, gridDim.x);
   const int ntn = (p.N + BN - 1) / BN;
   int tm, tn, z;
@@ -1263,15 +1258,13 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   const unsigned short* Bg = p.B3;
   // split-K (O_PHASE / O_DENSE): z = phase * (ksplit / kbpw) + workgroup slice of kbpw sign blocks
   const bool KSPLIT = OM != O_WGRAD && p.ksplit > 1;
-  // split-K into register-layout slabs (GemmArgs::kslab_reg; launched only split, 256 x 128 16x16-tile path): a
-  // compile-time variant, so the block-total registers of the unsplit kernel drop out
-  constexpr bool KREG = (V & 1048576) != 0;
-  static_assert(!KREG || (M16 && !(V & (32 | 2048 | 65536 | 131072 | 262144 | 524288))), "KREG: default tiles only");
+  constexpr bool KREG = (V & X3_KREG) != 0;  // register-layout slabs (launched only split)
+  static_assert(!KREG || !WIDE, "KREG: 256 x 128 tiles only");
   // in-GEMM ordered fix-up of the split-K slabs (round 6; the protocol is described where the epilogue runs it)
   constexpr bool FIXUP = (V & X3_FIXUP) != 0;
   static_assert(!FIXUP || (KREG && F32A), "FIXUP: the F32A register-slab split-K path");
   constexpr bool TSHARE = (V & X3_TAPSHARE) != 0;
-  static_assert(!TSHARE || (F32A && OM != O_WGRAD && !(V & 8)), "TAPSHARE: the F32A path on the slice-major walk");
+  static_assert(!TSHARE || F32A, "TAPSHARE: the F32A path (on the slice-major walk)");
   const int nslz = KSPLIT ? p.ksplit / p.kbpw : 1;
   const int zph = KSPLIT ? z / nslz : z, zsl = KSPLIT ? z - zph * nslz : 0;
   if (OM == O_PHASE) {
@@ -1316,11 +1309,9 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   // ---- per-thread chunks: chunk id = tid + 512 j -> (row id / 12, 16-B chunk id % 12)
   int abase[AJ];
   unsigned amask[AJ], boff[BJ];
-  int alds[AJ], blds[BJ];
 #pragma unroll
   for (int j = 0; j < AJ; ++j) {
-    // P16: 16-deep K stages, rows of 6 chunks in global order (the first X3P_AJ entries are used)
-    const int nch = F32A ? 8 : P16 ? 6 : X3_CHUNKS;
+    const int nch = F32A ? 8 : X3_CHUNKS;
     const int id = tid + 512 * j, row = id / nch, ch = id - row * nch;
     const int m = m0 + row;
     unsigned msk = 0;
@@ -1348,18 +1339,14 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
             msk |= 1u << (ky * kw + kx);
     }
     const int q = (ch / 3) ^ x3_swz(row), limb = ch - (ch / 3) * 3;  // logical octet of physical chunk ch
-    abase[j] = F32A ? base * 4 + ((id & 7) ^ f32a_swz(row & 15)) * 16
-                    : P16 ? base * 6 + ch * 16 : base * 6 + q * 48 + limb * 16;
+    abase[j] = F32A ? base * 4 + ((id & 7) ^ f32a_swz(row & 15)) * 16 : base * 6 + q * 48 + limb * 16;
     amask[j] = msk;
-    alds[j] = row * X3_ROWB + ch * 16;
   }
 #pragma unroll
   for (int j = 0; j < BJ; ++j) {
-    const int nch = P16 ? 6 : X3_CHUNKS;
-    const int id = tid + 512 * j, row = id / nch, ch = id - row * nch;
+    const int id = tid + 512 * j, row = id / X3_CHUNKS, ch = id - row * X3_CHUNKS;
     const int q = (ch / 3) ^ x3_swz(row), limb = ch - (ch / 3) * 3;
-    boff[j] = (unsigned)((n0 + row) * p.K * 6 + (P16 ? ch * 16 : q * 48 + limb * 16));  // rows >= N fall out of range
-    blds[j] = (BM + row) * X3_ROWB + ch * 16;
+    boff[j] = (unsigned)((n0 + row) * p.K * 6 + q * 48 + limb * 16);  // rows >= N fall out of range
   }
 
   int tap = 0, ci0 = 0, tky = 0, tkx = 0;
@@ -1412,47 +1399,6 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
       set_tap();
     }
   };
-  u32x4 ra[AJ], rb[BJ];
-  auto load_ab = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < AJ; ++j)
-      ra[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)aoff[j], ci0 * 6, 0));
-#pragma unroll
-    for (int j = 0; j < BJ; ++j)
-      rb[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)boff[j], k0 * 6, 0));
-    next_ktile();
-  };
-  auto store_ab = [&](int buf) {
-    unsigned char* base = smem + buf * (BM + BN) * X3_ROWB;
-#pragma unroll
-    for (int j = 0; j < AJ; ++j) *reinterpret_cast<u32x4*>(base + alds[j]) = ra[j];
-#pragma unroll
-    for (int j = 0; j < BJ; ++j) *reinterpret_cast<u32x4*>(base + blds[j]) = rb[j];
-  };
-  // channel-major walk: the next tile's (slice, tap), advanced after the tile's barrier (its VALU work then
-  // overlaps the trailing MFMAs; before the DMA issue it delayed the next tile, before the barrier it kept the
-  // barrier from being hoisted)
-  constexpr bool CMAJ = (V & 8) != 0 && OM != O_WGRAD;
-  constexpr int CMAJ_SW = X3_BK;  // channels per slice of the channel-major walk (64 measured the same)
-  int cmaj_h = 0;  // K tile within the current slice (slices of CMAJ_SW channels)
-  auto advance_cmaj = [&]() {
-    if (++cmaj_h < CMAJ_SW / X3_BK) {
-      ci0 += X3_BK;
-      return;
-    }
-    cmaj_h = 0;
-    ci0 -= CMAJ_SW - X3_BK;
-    ++tap;
-    if (++tkx == kw) {
-      tkx = 0;
-      if (++tky == kh) {
-        tky = 0;
-        tap = 0;
-        ci0 += CMAJ_SW;
-      }
-    }
-    set_tap();
-  };
   // LDS-DMA form: chunk id -> LDS byte 16 id, so each wave-instruction fills 1 KiB at a wave-uniform base
   typedef __attribute__((address_space(3))) void* lds_t;
   const int wbase = (tid & ~63) * 16;
@@ -1471,26 +1417,6 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(base + 512 * 16 * j), 16,
                                                  live ? (int)(abase[j] + k0 * 6) : (int)KM_OOB, 0, 0, 0);
       }
-    } else if constexpr (CMAJ) {
-      // K tile kt = (channel slice kt / taps, tap kt % taps), walked incrementally; the weights are stored in
-      // the same slice-major order (launch_split_x3_cmaj), so B stays the sequential column k0
-#pragma unroll
-      for (int j = 0; j < AJ; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(base + 512 * 16 * j), 16, (int)aoff[j], ci0 * ESZ, 0, 0);
-    } else if constexpr ((V & 16384) != 0) {
-      // timing probe (wrong results): no A DMA after the first tile
-      if (k0 == kbeg) {
-#pragma unroll
-        for (int j = 0; j < AJ; ++j)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(base + 512 * 16 * j), 16, (int)aoff[j], ci0 * 6, 0, 0);
-      }
-    } else if constexpr ((V & 4096) != 0) {
-      // timing probe (tools/gemm_bench.hip only, wrong results): every workgroup loads the same 64 KB, so the DMA
-      // is served by a hot L2 (issue cost and L2 latency only)
-#pragma unroll
-      for (int j = 0; j < AJ; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(base + 512 * 16 * j), 16, (tid * 16 + 8192 * j) & 0xFFFF,
-                                                 0, 0, 0);
     } else {
 #pragma unroll
       for (int j = 0; j < AJ; ++j)
@@ -1498,43 +1424,12 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     }
 #pragma unroll
     for (int j = 0; j < BJ; ++j)
-      if (!(V & 32768) || k0 == kbeg)  // 32768: timing probe (wrong results), no B DMA after the first tile
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_t)(base + BM * AROWB + 512 * 16 * j), 16,
-                                               (V & 4096) ? ((tid * 16 + 8192 * j) & 0xFFFF) : (int)boff[j],
-                                               (V & 4096) ? 0 : k0 * 6, 0, 0);
-    if constexpr (OM != O_WGRAD && !CMAJ) next_ktile();
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_t)(base + BM * AROWB + 512 * 16 * j), 16, (int)boff[j],
+                                               k0 * 6, 0, 0);
+    if constexpr (OM != O_WGRAD) next_ktile();
   };
 
-  // 65536 / 131072 (A/B): the default path's DMA in two parts, B and half of A at the tile start, the other half of A
-  // after a quarter / half of the tile's MFMAs
-  auto dma_part = [&](int k0, int buf, int part) {
-    unsigned char* base = smem + buf * (BM + BN) * X3_ROWB + wbase;
-    if (part == 0) {
-#pragma unroll
-      for (int j = 0; j < BJ; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_t)(base + BM * X3_ROWB + 512 * 16 * j), 16, (int)boff[j],
-                                                 k0 * 6, 0, 0);
-#pragma unroll
-      for (int j = 0; j < AJ / 2; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(base + 512 * 16 * j), 16, (int)aoff[j], ci0 * 6, 0, 0);
-    } else {
-#pragma unroll
-      for (int j = AJ / 2; j < AJ; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(base + 512 * 16 * j), 16, (int)aoff[j], ci0 * 6, 0, 0);
-      ci0 += X3_BK;
-      if (ci0 == Cg) {
-        ci0 = 0;
-        ++tap;
-        if (++tkx == kw) {
-          tkx = 0;
-          ++tky;
-        }
-        set_tap();
-      }
-    }
-  };
-
-  // Blocked accumulation: the MFMA chain runs over FLUSH K tiles, then adds into tot (a second fp32 sum
+  // Blocked accumulation: the MFMA chain runs over FLUSH K tiles, then adds into tot16 (a second fp32 sum
   // over the blocks, round-to-nearest VALU adds) and restarts from zero.  Rounding error of one output then
   // grows with sqrt(K/32 * FLUSH) + K/32/sqrt(FLUSH) instead of K/32: ~3x less at K = 16384
   // (tools/diag_hq.py), for 64 VGPRs and 64 v_add_f32 per FLUSH tiles.
@@ -1544,33 +1439,19 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   // its sign survives every later layer and the first layer's 32768-term sum where rounding noise cancels
   // (tools/diag_chain.py: 3x the CPU's error on CelebA-HQ's z gradient); with -B stored on odd blocks and
   // those blocks subtracted, consecutive blocks' biases cancel.
-  f32x16 acc[2][2], tot[2][2];
   f32x4 acc16[4][4], tot16[4][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = tot[i][j][r] = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc16[i][j] = tot16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // 32x32x16: fragment of k16 step s, lane half h = octet 2s + h of the row, limb l at +16 l
-  // 16x16x32: lane quarter q = octet q of the row (the whole 32-deep K tile in one MFMA)
-  // (tile bases are multiples of 16 rows, so the row swizzle is a function of lrow alone)
-  const int lrow = M16 ? (lane & 15) : (lane & 31), loct = M16 ? (lane >> 4) : (lane >> 5);
+  // a fragment's lane: row lrow of a 16-row tile, quarter loct = octet loct of the row (the whole 32-deep K tile in one
+  // MFMA); tile bases are multiples of 16 rows, so the row swizzle is a function of lrow alone
+  const int lrow = lane & 15, loct = lane >> 4;
   const int sw = x3_swz(lrow);
   const int afr = (wm * 64 + lrow) * X3_ROWB, bfr = (BM + wn * 64 + lrow) * X3_ROWB;
-  const int oct16 = (loct ^ sw) * 48;                                         // 16x16x32
-  const int oct32[2] = {((loct) ^ sw) * 48, ((2 + loct) ^ sw) * 48};          // 32x32x16, k16 step s
+  const int oct16 = (loct ^ sw) * 48;
 
-  // 128: static priority for the younger half of the workgroup (waves 4-7 lose VALU / LDS issue arbitration to
-  // their older SIMD partners at every tile start; MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  if constexpr ((V & 128) != 0) {
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-  }
   auto flush16 = [&](int ktd) {  // block flush after the MFMAs of K tile ktd
     const float sg = (p.b_negblk && (((ktd + kt0) >> FLOG) & 1)) ? -1.f : 1.f;
 #pragma unroll
@@ -1893,201 +1774,36 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
       tile(kt, fx, fy);
       if (kt + 1 < nk) tile(kt + 1, fy, fx);
     }
-  } else if constexpr (P16) {
-    // ---- 16-deep K stages: stage s (16 k) of the A and B tiles is 384 rows x 96 B (three limbs of two octets, global
-    // order, conflict-free for every fragment pattern below without a swizzle), slot s & 3 of a 4-slot ring; the DMA
-    // of stage s + 3 is issued at the start of stage s, so three stages are in flight across each raw barrier and a
-    // wave waits (counted vmcnt) only for the stage the next one reads.  Per (A tile, B tile) three MFMAs, each over 16
-    // k of two limb products: [h|l].[l|h] (hl + lh), [h|m].[m|h] (hm + mh), [h|m].[h|m] (hh + mm).
-    static_assert(DMA_OK_P16 && !CMAJ && M16, "P16: LDS-DMA, tap-major walk, 16x16 tiles");
-    constexpr int PROWB = 96, PSLOT = (BM + BN) * PROWB;
-    static_assert(4 * PSLOT <= 2 * (BM + BN) * X3_ROWB, "P16 ring exceeds the LDS");
-    const int nks = 2 * nk;
-    const bool lo4 = __builtin_amdgcn_readfirstlane(tid) < 256;  // waves 0-3 also issue the second B piece
-    auto pdma = [&](int s) {
-      const int k0 = kbeg + s * 16;
-      unsigned char* base = smem + (s & 3) * PSLOT + wbase;
-      if constexpr (OM == O_WGRAD) {
-        const int pix = k0 / p.wg_bp;
-        const int qy = pix / Win, qx = pix - qy * Win;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const int dy = (int)(amask[j] & 3u) - 1, dx = (int)((amask[j] >> 2) & 3u) - 1;
-          const bool live = amask[j] != 0xFFFFFFFFu && (unsigned)(qy + dy) < (unsigned)p.Hin &&
-                            (unsigned)(qx + dx) < (unsigned)Win;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(base + 512 * 16 * j), 16,
-                                                   live ? (int)(abase[j] + k0 * 6) : (int)KM_OOB, 0, 0, 0);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(base + 512 * 16 * j), 16, (int)aoff[j], ci0 * 6, 0, 0);
-      }
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_t)(base + BM * PROWB), 16, (int)boff[0], k0 * 6, 0, 0);
-      if (lo4)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_t)(base + BM * PROWB + 512 * 16), 16, (int)boff[1], k0 * 6,
-                                                 0, 0);
-      if constexpr (OM != O_WGRAD) {
-        ci0 += 16;
-        if (ci0 == Cg) {
-          ci0 = 0;
-          ++tap;
-          if (++tkx == kw) {
-            tkx = 0;
-            ++tky;
-          }
-          set_tap();
-        }
-      }
-    };
-    // wait until at most `younger` stage groups issued after the one needed are still in flight (5 pieces per stage
-    // on waves 0-3, 4 on waves 4-7)
-    auto vwait = [&](int younger) {
-      if (lo4) {
-        if (younger >= 2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else {
-        if (younger >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    };
-    for (int s = 0; s < 3; ++s)
-      if (s < nks) pdma(s);
-    vwait((1 < nks) + (2 < nks));
-    __builtin_amdgcn_s_barrier();
-    // fragment byte offsets of this lane: row m = lane & 15, k-group q = lane >> 4 reads octet q & 1 of limb h (q < 2)
-    // or the pattern's second limb
-    const int lrow16 = lane & 15, q4 = lane >> 4, o3 = (q4 & 1) * 3;
-    const int cA1 = (o3 + (q4 < 2 ? 0 : 1)) * 16, cA2 = (o3 + (q4 < 2 ? 0 : 2)) * 16;
-    const int cB2 = (o3 + (q4 < 2 ? 1 : 0)) * 16, cB3 = (o3 + (q4 < 2 ? 2 : 0)) * 16;
-    const int arow = (wm * 64 + lrow16) * PROWB, brow = (BM + wn * 64 + lrow16) * PROWB;
-    bf16x8 fa1[4], fa2[4], fb1[4], fb2[4], fb3[4];
-    constexpr int SG_MFMA = 0x8, SG_DS_RD = 0x100;
-    for (int s = 0; s < nks; ++s) {
-      if (s + 3 < nks) pdma(s + 3);
-      const unsigned char* sb = smem + (s & 3) * PSLOT;
-      auto rd_a = [&](int t) {
-        fa1[t] = *reinterpret_cast<const bf16x8*>(sb + arow + t * 16 * PROWB + cA1);
-        fa2[t] = *reinterpret_cast<const bf16x8*>(sb + arow + t * 16 * PROWB + cA2);
-      };
-      auto rd_b = [&](int t) {
-        fb1[t] = *reinterpret_cast<const bf16x8*>(sb + brow + t * 16 * PROWB + cA1);
-        fb2[t] = *reinterpret_cast<const bf16x8*>(sb + brow + t * 16 * PROWB + cB2);
-        fb3[t] = *reinterpret_cast<const bf16x8*>(sb + brow + t * 16 * PROWB + cB3);
-      };
-      auto mf = [&](int i, int j) {
-        f32x4 c = acc16[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa2[i], fb3[j], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1[i], fb2[j], c, 0, 0, 0);
-        acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1[i], fb1[j], c, 0, 0, 0);
-      };
-      rd_a(0);
-      rd_b(0);
-      rd_b(1);
-      mf(0, 0);
-      rd_b(2);
-      mf(0, 1);
-      rd_b(3);
-      mf(0, 2);
-      rd_a(1);
-      mf(0, 3);
-      rd_a(2);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mf(1, j);
-      rd_a(3);
-#pragma unroll
-      for (int i = 2; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mf(i, j);
-      __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 8, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 3, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 12, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 24, 0);
-      // the next stage's DMA has landed (this wave's pieces; the barrier covers the other waves'), and this stage's
-      // reads are retired before any wave re-fills its slot
-      vwait((s + 2 < nks) + (s + 3 < nks));
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (!(V & 32) && ((s + 1) & (2 * FLUSH - 1)) == 0) flush16(s >> 1);
-    }
   } else {
-  constexpr bool DMA = (V & 4) != 0;
-  static_assert(OM != O_WGRAD || DMA, "O_WGRAD runs on the LDS-DMA staging path only");
-  static_assert(!CMAJ || DMA, "the channel-major walk runs on the LDS-DMA staging path only");
-  if (DMA) {
+    // ---- the limb A image (X3_BASE alone, X3_WIDE, X3_KREG; the only O_WGRAD path): each wave 4 x 4 tiles of 16 x 16
     if (nk > 0) dma_ab(kbeg, 0);
-    if constexpr (CMAJ) advance_cmaj();
-  } else if (nk > 0) {
-    load_ab(0);
-    store_ab(0);
-    if (nk > 1) load_ab(X3_BK);
-  }
-  __syncthreads();
-  bf16x8 pfa[4][3], pfb[4][3];  // the read-order path's fragments
-  // 2048: waves 4-7 run half a tile behind (the stagger of MI355X_MICROARCH.md, two waves per SIMD, item 9); every
-  // accumulator still takes its tiles' MFMAs in the same order and is flushed at the same block ends: bitwise the
-  // unstaggered kernel
-  const bool stag = M16 && (V & 256) && (V & 2048) && DMA && __builtin_amdgcn_readfirstlane(tid) >= 256;
-
-  auto mfp = [&](int i, int j) {  // the six limb products of A tile i x B tile j, smallest first
-    f32x4 c = acc16[i][j];
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfa[i][2], pfb[j][0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfa[i][1], pfb[j][1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfa[i][0], pfb[j][2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfa[i][1], pfb[j][0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfa[i][0], pfb[j][1], c, 0, 0, 0);
-    acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfa[i][0], pfb[j][0], c, 0, 0, 0);
-  };
-  // one loop per wave role (a runtime branch inside a shared loop made the compiler keep both roles' fragment sets
-  // live: 316 VGPRs spilled)
-  auto kloop = [&](auto S_) {
-    constexpr bool S = decltype(S_)::value;
-    for (int kt = 0; kt < nk; ++kt) {
-      const unsigned char* base = smem + (kt & 1) * (BM + BN) * X3_ROWB;
-      // DMA: the next tile goes into the other buffer (read before the previous barrier) now; the
-      // barrier at the end of this tile (its vmcnt(0)) lands it
-      // (issuing it later — after the fragment reads, or mid-MFMA — measured 10-15 % slower)
-      // timing probes (tools/gemm_bench.hip only, wrong results): 512 no DMA after the first tile, 1024 fragment reads
-      // of the first tile only
-      // 8192 (with the stagger): the staggered waves issue their share of the DMA after their trailing half tile, so
-      // the two waves of a SIMD never issue DMA at the same time (each covers the other's DMA issue with MFMAs)
-      constexpr bool LATE = S && (V & 8192) != 0;
-      constexpr int SPLIT = (V & 65536) ? 1 : (V & 131072) ? 2 : 0;
-      static_assert(SPLIT == 0 || (OM != O_WGRAD && !CMAJ && !(V & (512 | 2048 | 4096 | 16384 | 32768))), "probe mix");
-      const bool dnext = DMA && kt + 1 < nk && !(V & 512);
-      if (SPLIT && dnext) dma_part(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1, 0);
-      else if (dnext && !(LATE && kt > 0)) dma_ab(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1);
-      if (M16 && (V & 256)) {
-        // 256: fragment reads one group ahead of the MFMAs that consume them, in the order those MFMAs run (A tile 0
-        // against B tiles 0..3, then A tiles 1..3), pinned by sched_group_barrier: the first MFMAs wait for 6 reads
-        // instead of the ~15 the default schedule puts in front of its first lgkmcnt(0).  2.5-3.9 % less time on
-        // the four CIFAR shapes, bit-identical results (profiles/r02/gemm_bench_rdorder.txt).  Measured and dropped:
-        // reading the next tile's first fragments after the barrier into the registers the trailing MFMAs free
-        // (cross-tile pipeline, 1-2 % slower than this), all reads issued by the end of A row 0 so the barrier moves
-        // up (5-8 % slower), A tile 3 read later so it moves down (0-2 % slower).
-        bf16x8 (&fa)[4][3] = pfa, (&fb)[4][3] = pfb;  // [tile][limb]
-        const bool rd = !(V & 1024) || kt == 0;
+    __syncthreads();
+    bf16x8 fa[4][3], fb[4][3];  // [tile][limb]
+    // (the loop stays a lambda: written as a plain loop in the kernel body, hipcc orders the prologue and allocates
+    // registers differently in every instantiation of this path; DESIGN.md, retired variant bits)
+    auto kloop = [&]() {
+      for (int kt = 0; kt < nk; ++kt) {
+        const unsigned char* base = smem + (kt & 1) * BUFB;
+        // the next tile goes into the other buffer (read before the previous barrier) now; the barrier at the end of
+        // this tile (its vmcnt(0)) lands it (issuing it later -- after the fragment reads, or mid-MFMA -- measured
+        // 10-15 % slower)
+        if (kt + 1 < nk) dma_ab(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1);
+        // fragment reads one group ahead of the MFMAs that consume them, in the order those MFMAs run (A tile 0 against
+        // B tiles 0..3, then A tiles 1..3), pinned by sched_group_barrier: the first MFMAs wait for 6 reads instead of
+        // the ~15 the compiler's own schedule puts in front of its first lgkmcnt(0).  2.5-3.9 % less time on the four
+        // CIFAR shapes, bit-identical results (profiles/r02/gemm_bench_rdorder.txt).  Measured and dropped: reading the
+        // next tile's first fragments after the barrier into the registers the trailing MFMAs free (cross-tile pipeline,
+        // 1-2 % slower than this), all reads issued by the end of A row 0 so the barrier moves up (5-8 % slower), A tile
+        // 3 read later so it moves down (0-2 % slower).
         auto rd_a = [&](int t) {
-          if (!rd) return;
 #pragma unroll
           for (int l = 0; l < 3; ++l) fa[t][l] = *reinterpret_cast<const bf16x8*>(base + afr + t * 16 * X3_ROWB + oct16 + l * 16);
         };
         auto rd_b = [&](int t) {
-          if (!rd) return;
 #pragma unroll
           for (int l = 0; l < 3; ++l) fb[t][l] = *reinterpret_cast<const bf16x8*>(base + bfr + t * 16 * X3_ROWB + oct16 + l * 16);
         };
-        auto mf = [&](int i, int j) {
+        auto mf = [&](int i, int j) {  // the six limb products of A tile i x B tile j, smallest first
           f32x4 c = acc16[i][j];
           c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);
           c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[j][1], c, 0, 0, 0);
@@ -2097,88 +1813,6 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
           acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][0], c, 0, 0, 0);
         };
         constexpr int SG_MFMA = 0x8, SG_DS_RD = 0x100;
-        if constexpr (S) {
-          // 2048, waves 4-7: the second half (A tiles 2, 3) of the previous tile's MFMAs from the registers its
-          // fragments still hold, that tile's block flush, then this tile's reads and its first half, so that on every
-          // SIMD one wave is at MFMAs while its partner waits for its fragment reads after the barrier
-          if (kt > 0) {
-#pragma unroll
-            for (int i = 2; i < 4; ++i)
-#pragma unroll
-              for (int j = 0; j < 4; ++j) mf(i, j);
-            __builtin_amdgcn_sched_barrier(0);
-            if (!(V & 32) && (kt & (FLUSH - 1)) == 0) flush16(kt - 1);
-            if (LATE && kt + 1 < nk && !(V & 512)) dma_ab(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1);
-          }
-          rd_a(0);
-          rd_b(0);
-          rd_b(1);
-          mf(0, 0);
-          rd_b(2);
-          mf(0, 1);
-          rd_b(3);
-          mf(0, 2);
-          rd_a(1);
-          mf(0, 3);
-          rd_a(2);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) mf(1, j);
-          rd_a(3);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 9, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 6, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 6, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 6, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 6, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 24, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __syncthreads();
-          if constexpr (CMAJ) advance_cmaj();
-          continue;
-        }
-        if constexpr (SPLIT != 0) {
-          rd_a(0);
-          rd_b(0);
-          rd_b(1);
-          mf(0, 0);
-          rd_b(2);
-          mf(0, 1);
-          rd_b(3);
-          mf(0, 2);
-          rd_a(1);
-          mf(0, 3);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 9, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 6, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 6, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 6, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 6, 0);
-          __builtin_amdgcn_sched_barrier(0);
-          if (SPLIT == 1 && dnext) dma_part(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1, 1);
-          __builtin_amdgcn_sched_barrier(0);
-          rd_a(2);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) mf(1, j);
-          rd_a(3);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 24, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          __builtin_amdgcn_sched_barrier(0);
-          if (SPLIT == 2 && dnext) dma_part(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1, 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 2; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) mf(i, j);
-          __syncthreads();
-          if (!(V & 32) && ((kt + 1) & (FLUSH - 1)) == 0) flush16(kt);
-          continue;
-        }
         rd_a(0);
         rd_b(0);
         rd_b(1);
@@ -2209,129 +1843,38 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         __builtin_amdgcn_sched_group_barrier(SG_MFMA, 24, 0);
         __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
         __builtin_amdgcn_sched_group_barrier(SG_MFMA, 48, 0);
-      } else if (M16) {
-        bf16x8 fa[4][3], fb[4][3];  // [tile][limb]
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int l = 0; l < 3; ++l) {
-            fa[t][l] = *reinterpret_cast<const bf16x8*>(base + afr + t * 16 * X3_ROWB + oct16 + l * 16);
-            fb[t][l] = *reinterpret_cast<const bf16x8*>(base + bfr + t * 16 * X3_ROWB + oct16 + l * 16);
-          }
-        if (!DMA && kt + 1 < nk) {
-          store_ab((kt + 1) & 1);
-          if (kt + 2 < nk) load_ab((kt + 2) * X3_BK);
-        }
-        if (V & 2) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            f32x4 c = acc16[i][j];
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[j][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][2], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fb[j][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][1], c, 0, 0, 0);
-            acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fb[j][0], c, 0, 0, 0);
-          }
-        if (V & 2) __builtin_amdgcn_s_setprio(0);
-      } else {
-        bf16x8 fa[2][2][3], fb[2][2][3];  // [s][tile][limb]
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int l = 0; l < 3; ++l) {
-              fa[s][t][l] = *reinterpret_cast<const bf16x8*>(base + afr + t * 32 * X3_ROWB + oct32[s] + l * 16);
-              fb[s][t][l] = *reinterpret_cast<const bf16x8*>(base + bfr + t * 32 * X3_ROWB + oct32[s] + l * 16);
-            }
-        if (!DMA && kt + 1 < nk) {
-          store_ab((kt + 1) & 1);
-          if (kt + 2 < nk) load_ab((kt + 2) * X3_BK);
-        }
-        if (V & 2) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              f32x16 c = acc[i][j];
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][2], fb[s][j][0], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][1], fb[s][j][1], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][0], fb[s][j][2], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][1], fb[s][j][0], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][0], fb[s][j][1], c, 0, 0, 0);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][0], fb[s][j][0], c, 0, 0, 0);
-            }
-        if (V & 2) __builtin_amdgcn_s_setprio(0);
-      }
-      __syncthreads();
-      if constexpr (CMAJ) advance_cmaj();
-      // block flush after the barrier: the compiler keeps hoisting the barrier above the tile's trailing MFMAs
-      // (a flush between them and the barrier measured 6-8 % slower)
-      if (KREG) {
-        if (((kt + 1) & (FLUSH - 1)) != 0) continue;
-        // split-K: every sign block's signed sum straight from the accumulators into its own slab, in the register
-        // layout (one 16-B store per lane and tile: 1 KB per wave-instruction); x3_ksplit_reduce_kernel maps back
-        // buffer stores: one VGPR of offset (wave, lane), the rest scalar, so the 256 accumulator VGPRs do not spill
-        const float sg = (p.b_negblk && (((kt + kt0) >> FLOG) & 1)) ? -1.f : 1.f;
-        const int ntile = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-        const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(p.kslab + ((long)zph * p.ksplit + zsl * p.kbpw) * ntile * (BM * BN)), (short)0,
-            p.kbpw * ntile * (BM * BN) * 4, 0x00020000);
-        const int soff = ((kt >> FLOG) * ntile + tm * ntn + tn) * (BM * BN * 4);
-        const int voff = (wave * 1024 + lane) * 16;
-        const bool live = m0 + wm * 64 < p.M;  // a wave whose 64 rows are all past M stores nothing (the reduce skips them)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            acc16[i][j] *= sg;
-            if (live)
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc16[i][j]), rsl, voff,
-                                                     soff + (i * 4 + j) * 1024, 0);
-            acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-          }
-      } else if (!(V & 32) && ((kt + 1) & (FLUSH - 1)) == 0) {
-        const float sg = (p.b_negblk && (((kt + kt0) >> FLOG) & 1)) ? -1.f : 1.f;
-        if (M16) {
+        __syncthreads();
+        // block flush after the barrier: the compiler keeps hoisting the barrier above the tile's trailing MFMAs
+        // (a flush between them and the barrier measured 6-8 % slower)
+        if (KREG) {
+          if (((kt + 1) & (FLUSH - 1)) != 0) continue;
+          // split-K: every sign block's signed sum straight from the accumulators into its own slab, in the register
+          // layout (one 16-B store per lane and tile: 1 KB per wave-instruction); x3_ksplit_reduce_kernel maps back
+          // buffer stores: one VGPR of offset (wave, lane), the rest scalar, so the 256 accumulator VGPRs do not spill
+          const float sg = (p.b_negblk && (((kt + kt0) >> FLOG) & 1)) ? -1.f : 1.f;
+          const int ntile = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+          const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc(
+              (void*)(p.kslab + ((long)zph * p.ksplit + zsl * p.kbpw) * ntile * (BM * BN)), (short)0,
+              p.kbpw * ntile * (BM * BN) * 4, 0x00020000);
+          const int soff = ((kt >> FLOG) * ntile + tm * ntn + tn) * (BM * BN * 4);
+          const int voff = (wave * 1024 + lane) * 16;
+          const bool live = m0 + wm * 64 < p.M;  // a wave whose 64 rows are all past M stores nothing (the reduce skips them)
 #pragma unroll
           for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) tot16[i][j][r] = __builtin_fmaf(sg, acc16[i][j][r], tot16[i][j][r]);
+              acc16[i][j] *= sg;
+              if (live)
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc16[i][j]), rsl, voff,
+                                                       soff + (i * 4 + j) * 1024, 0);
               acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) {
-                tot[i][j][r] = __builtin_fmaf(sg, acc[i][j][r], tot[i][j][r]);
-                acc[i][j][r] = 0.f;
-              }
+        } else if (((kt + 1) & (FLUSH - 1)) == 0) {
+          flush16(kt);
         }
       }
-    }
-    if (S && nk > 0) {  // the staggered waves' trailing half tile
-#pragma unroll
-      for (int i = 2; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mfp(i, j);
-      if (!(V & 32) && (nk & (FLUSH - 1)) == 0) flush16(nk - 1);
-    }
-  };
-  if (stag)
-    kloop(std::true_type{});
-  else
-    kloop(std::false_type{});
-
+    };
+    kloop();
   }
   if (p.clk && tid == 0) {  // the K loop's shader clocks over its 100 MHz ticks (damc_clock_probe)
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -2344,22 +1887,13 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   if (KREG && !FIXUP) return;  // every block already in its slab
   if constexpr (!FIXUP) {  // the last partial block
     const float sg = (p.b_negblk && nk > 0 && (((nk - 1 + kt0) >> FLOG) & 1)) ? -1.f : 1.f;
-    if (M16) {
-      constexpr int MI = NARROW ? 2 : 4;
+    constexpr int MI = NARROW ? 2 : 4;
 #pragma unroll
-      for (int i = 0; i < MI; ++i)
+    for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < MI; ++j)
+      for (int j = 0; j < MI; ++j)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc16[i][j][r] = __builtin_fmaf(sg, acc16[i][j][r], tot16[i][j][r]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = __builtin_fmaf(sg, acc[i][j][r], tot[i][j][r]);
-    }
+        for (int r = 0; r < 4; ++r) acc16[i][j][r] = __builtin_fmaf(sg, acc16[i][j][r], tot16[i][j][r]);
   }
   // ---- epilogue through LDS: the block's 256 x 128 fp32 tile, then one thread per (row, channel octet):
   // 2 x 16-B fp32 stores and (C3) 3 x 16-B limb stores per octet, each row's 128 channels contiguous
@@ -2657,7 +2191,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           tile[(wm * 32 + i * 16 + 4 * (lane >> 4) + r) * TS + wn * 32 + j * 16 + (lane & 15)] = acc16[i][j][r];
-  } else if (M16) {
+  } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -2665,15 +2199,6 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           tile[(wm * 64 + i * 16 + 4 * (lane >> 4) + r) * TS + wn * 64 + j * 16 + (lane & 15)] = acc16[i][j][r];
-  } else {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          tile[(wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * TS + wn * 64 + j * 32 + (lane & 31)] =
-              acc[i][j][r];
   }
   __syncthreads();
   if (KSPLIT && !FIXUP) {  // row-major slabs (one block per workgroup): the fp32 tile into its slab; the reduce applies the epilogue
@@ -3079,7 +2604,7 @@ int x3_ksplit(int M, int N, int K, int zdim, int bm, int bn, int negk = X3_NEGK)
   return split ? ks : 1;
 }
 
-long x3_ksplit_floats(int M, int N, int K, int zdim, int negk) {  // either block layout (gemm_x3_kernel, V & 524288)
+long x3_ksplit_floats(int M, int N, int K, int zdim, int negk) {  // either block layout (gemm_x3_kernel, X3_WIDE)
   const int ks = std::max(x3_ksplit(M, N, K, zdim, X3_BM, X3_BN, negk), x3_ksplit(M, N, K, zdim, 128, 256, negk));
   // the register slab layout covers whole 256 x 128 tiles
   const long padded = (long)((M + X3_BM - 1) / X3_BM) * X3_BM * ((N + X3_BN - 1) / X3_BN) * X3_BN;
@@ -3103,9 +2628,15 @@ static bool x3_tapshare_on() {
   return !(e && e[0] == '0');
 }
 
-template <int EPI, int OM, int V = DAMC_X3_VARIANT>
+// V: X3_BASE, + X3_F32A, or + X3_WIDE, as launch_gemm_x3 chooses; X3_TAPSHARE, X3_NARROW, X3_KREG, X3_FIXUP and
+// X3_RASTER are added here
+template <int EPI, int OM, int V = X3_BASE>
 static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
-  if constexpr ((V & X3_F32A) != 0 && !(V & (8 | 16 | X3_TAPSHARE)) &&
+  static_assert(OM != O_WGRAD && (V & X3_BASE) == X3_BASE && !(V & ~(X3_BASE | X3_F32A | X3_WIDE | X3_TAPSHARE)) &&
+                    !((V & X3_WIDE) && (V & X3_F32A)),
+                "the caller picks the operand form and the tile; the other variants are chosen below");
+  constexpr bool F32A = (V & X3_F32A) != 0, WIDE = (V & X3_WIDE) != 0;
+  if constexpr (F32A && !(V & X3_TAPSHARE) &&
                 ((EPI == EPI_BIAS_ACT && OM == O_PHASE) || ((EPI == EPI_MASK || EPI == EPI_STORE) && OM == O_DENSE))) {
     if (a0.tapshare && x3_tapshare_on() && x3_tapshare_shape(a0, (OMode)OM)) {
       g_tapshare_launches.fetch_add(1, std::memory_order_relaxed);
@@ -3113,7 +2644,7 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
     }
   }
   GemmArgs a = a0;
-  constexpr int BM = (V & 524288) ? 128 : X3_BM, BN = (V & 524288) ? 256 : X3_BN;
+  constexpr int BM = WIDE ? 128 : X3_BM, BN = WIDE ? 256 : X3_BN;
   const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
   // the norm statistics in the epilogue (GemmArgs::in_part): the unsplit 256 x 128 dense tile only; every other launch
   // clears in_done and leaves them to the caller's kernel
@@ -3121,10 +2652,10 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
     if (a.in_part && a.in_done) *a.in_done = 0;
     a.in_part = nullptr;
   };
-  if (a.in_part && !(OM == O_DENSE && EPI == EPI_BIAS_ACT && BM == 256 && BN == 128 && zdim == 1 && a.in_hw > 0 &&
+  if (a.in_part && !(OM == O_DENSE && EPI == EPI_BIAS_ACT && !WIDE && zdim == 1 && a.in_hw > 0 &&
                      a.in_hw % 256 == 0 && a.M % a.in_hw == 0 && a.in_S == a.in_hw / 256))
     no_stats();
-  if constexpr (V == DAMC_X3_VARIANT && OM != O_WGRAD) {
+  if constexpr (V == X3_BASE) {
     // opt-in (DAMC_X3_NARROW=1, read per call): an under-filled grid that the 64 x 128 tile fills (>= 256 workgroups)
     // runs unsplit on it instead of split-K.  Measured slower at the CIFAR B=16 per-rank step: 158.7 / 152.2 us for the
     // L2 forward / L3 dgrad against 121 / 122 us for split-K + reduce (profiles/r04/b16_narrow_kernel_stats.csv): the
@@ -3137,12 +2668,12 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
       a.ksplit = 1;
       a.kbpw = 1;
       a.kslab_reg = 0;
-      hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, (V & ~(8 | 16)) | X3_NARROW>), dim3((unsigned)(nnm * ntn), 1, zdim), dim3(512), 0, s,
-                         a);
+      hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, X3_BASE | X3_NARROW>), dim3((unsigned)(nnm * ntn), 1, zdim), dim3(512),
+                         0, s, a);
       return 0;
     }
   }
-  if (OM != O_WGRAD && a.kslab && !(V & 16)) {
+  if (a.kslab) {
     const int ks = x3_ksplit(a.M, a.N, a.K, zdim, BM, BN, a.negk);
     if (ks > 1 && (long)zdim * ks * a.M * a.N <= a.kslab_floats && a.N % 8 == 0) {
       no_stats();
@@ -3156,9 +2687,9 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
         return 0;
       };
       // sign blocks per workgroup: the most (a power of two dividing ks) that still leaves >= 256 workgroups, so one
-      // round covers the chip (the default 16x16-tile path only); DAMC_X3_KSPLIT_BPW (read per call) pins it
+      // round covers the chip (256 x 128 tiles only); DAMC_X3_KSPLIT_BPW (read per call) pins it
       int bpw = 1;
-      if ((V & ~(X3_F32A | X3_TAPSHARE)) == DAMC_X3_VARIANT && (V & 1) && !(V & (2048 | 65536 | 131072 | 262144))) {
+      if (!WIDE) {
         const char* eb = getenv("DAMC_X3_KSPLIT_BPW");
         if (eb) {
           bpw = std::max(1, atoi(eb));
@@ -3167,19 +2698,17 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
           while (ks % (2 * bpw) == 0 && (long)ntm * ntn * zdim * ks / (2 * bpw) >= 256) bpw *= 2;
         }
       }
-      // the register slab layout on the default 16x16-tile path (256 x 128 tiles), row-major slabs (one block per
-      // workgroup) otherwise; DAMC_X3_KSLAB_REG=0, read per call, forces row-major
+      // the register slab layout on 256 x 128 tiles (X3_KREG), row-major slabs (one block per workgroup) otherwise;
+      // DAMC_X3_KSLAB_REG=0, read per call, forces row-major
       const char* er = getenv("DAMC_X3_KSLAB_REG");
-      a.kslab_reg = (!(er && er[0] == '0') && BM == X3_BM && BN == X3_BN && (V & 1) && (V & 4) &&
-                     !(V & (32 | 2048 | 65536 | 131072 | 262144)) && (long)zdim * ks * ntm * ntn * BM * BN <= a.kslab_floats &&
+      a.kslab_reg = (!(er && er[0] == '0') && !WIDE && (long)zdim * ks * ntm * ntn * BM * BN <= a.kslab_floats &&
                      (long)bpw * ntm * ntn * BM * BN * 4 < (1L << 31))
                         ? 1 : 0;
       if (!a.kslab_reg) bpw = 1;
       a.kbpw = bpw;
       a.k_per_z = a.K / ks * bpw;
-      if constexpr ((V & ~(X3_F32A | X3_TAPSHARE)) == DAMC_X3_VARIANT && OM != O_WGRAD && (V & 1) && (V & 4) &&
-                    !(V & (32 | 2048 | 65536 | 131072 | 262144 | 524288))) {
-        if constexpr ((V & X3_F32A) != 0 && ((EPI == EPI_BIAS_ACT && OM == O_PHASE) || (EPI == EPI_MASK && OM == O_DENSE))) {
+      if constexpr (!WIDE) {
+        if constexpr (F32A && ((EPI == EPI_BIAS_ACT && OM == O_PHASE) || (EPI == EPI_MASK && OM == O_DENSE))) {
           // round 6, opt-in (DAMC_X3_FIXUP=1, read per call): the in-GEMM ordered fix-up instead of the reduce launch
           // (bitwise; gemm_x3_kernel X3_FIXUP) where the caller provides zeroed counters.  Measured slower at every
           // per-rank batch (CIFAR B=16 0.474-0.485 against 0.410 ms per step, SVHN B=64 0.386-0.391 against
@@ -3193,20 +2722,17 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
             a.kepoch = ++*a.kepoch_ctr;  // this launch's tag on the counters and claims (16 bits; zeroed per call)
             a.fixup_probe = g_fixup_probe;
             a.proj_nostore = nostore0;  // the epilogue runs the fused projection itself, as the unsplit kernel does
-            hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V | 1048576 | X3_FIXUP>), dim3(ntm * ntn, 1, zdim * ks / bpw),
+            hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V | X3_KREG | X3_FIXUP>), dim3(ntm * ntn, 1, zdim * ks / bpw),
                                dim3(512), 0, s, a);
             return 0;
           }
         }
         if (a.kslab_reg)
-          hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V | 1048576>), dim3(ntm * ntn, 1, zdim * ks / bpw), dim3(512), 0,
+          hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V | X3_KREG>), dim3(ntm * ntn, 1, zdim * ks / bpw), dim3(512), 0,
                              s, a);
-        else
-          hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V>), dim3(ntm * ntn, 1, zdim * ks / bpw), dim3(512), 0, s, a);
-      } else {
-        a.kslab_reg = 0;
-        hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V>), dim3(ntm * ntn, 1, zdim * ks / bpw), dim3(512), 0, s, a);
       }
+      if (!a.kslab_reg)
+        hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V>), dim3(ntm * ntn, 1, zdim * ks / bpw), dim3(512), 0, s, a);
       if (a.kslab_reg) {  // one wave per 16x16 tile, four per workgroup
         if (EPI == EPI_BIAS_ACT && OM == O_DENSE && a.ksplit_deferred && !a.C3 && !a.sgn) {
           *a.ksplit_deferred = ks;  // the consumer sums the slabs (GemmArgs::ksplit_deferred)
@@ -3240,21 +2766,19 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
   a.ksplit = 1;
   a.kbpw = 1;
   a.kslab_reg = 0;
-  if constexpr ((V & X3_F32A) != 0 && OM == O_PHASE && !(V & 16)) {
-    // round 5: the unsplit F32A ConvT forward on the supertile raster (bit 16: each XCD's concurrent workgroups cover
+  if constexpr (F32A && OM == O_PHASE) {
+    // round 5: the unsplit F32A ConvT forward on the supertile raster (X3_RASTER: each XCD's concurrent workgroups cover
     // <= 8 M tiles x the 4 phases of an N tile, so the phases' overlapping input windows and weight panels are shared
     // in its L2).  Bitwise the default raster; CIFAR B=128 upconv_fwd FETCH 1059 -> 705 MB per launch at the same
     // time (548 vs 551 us; profiles/r05/walk_ab.txt).  DAMC_X3_RASTER=0 (read per call) keeps the default raster
     const char* er = getenv("DAMC_X3_RASTER");
     if (!(er && er[0] == '0')) {
-      hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V | 16>), dim3(ntm * ntn * zdim, 1, 1), dim3(512), 0, s, a);
+      // the phases folded into a 1-D grid
+      hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V | X3_RASTER>), dim3(ntm * ntn * zdim, 1, 1), dim3(512), 0, s, a);
       return 0;
     }
   }
-  if ((V & 16) && OM != O_WGRAD)  // supertile raster: phases folded into a 1-D grid
-    hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V>), dim3(ntm * ntn * zdim, 1, 1), dim3(512), 0, s, a);
-  else
-    hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V>), dim3(ntm * ntn, 1, zdim), dim3(512), 0, s, a);
+  hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V>), dim3(ntm * ntn, 1, zdim), dim3(512), 0, s, a);
   return 0;
 }
 
@@ -3300,7 +2824,8 @@ int launch_split_x3_negblk(const float* x, long n, int K, unsigned short* y, hip
 }
 
 // weight rows of K = taps * Cg values in tap-major order [tap][c] -> x3 in slice-major order
-// [c / 32][tap][c % 32] (the channel-major K walk, V & 8), odd negk-blocks of the new order negated
+// [c / sw][tap][c % sw] (the slice-major K walk, GemmArgs::kwalk, of a ConvT phase's forward weights), odd negk-blocks
+// of the new order negated
 __global__ void split_x3_cmaj_kernel(const float* __restrict__ x, long n8, int K8, int Cg8, int taps, int sw8,
                                      unsigned short* __restrict__ y, int negk) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // source octet
@@ -3365,7 +2890,6 @@ int launch_split_x3_walk(const float* x, long n, int K, int Cg, unsigned short* 
 }
 
 int launch_split_x3_conv(const float* x, long n, int K, int Cg, unsigned short* y, hipStream_t s, int negk) {
-  if ((DAMC_X3_VARIANT & 8) != 0 && Cg % 32 == 0) return launch_split_x3_cmaj(x, n, K, Cg, 32, y, s, negk);
   return launch_split_x3_negblk(x, n, K, y, s, negk);
 }
 
@@ -3451,8 +2975,7 @@ __global__ void __launch_bounds__(256) pack_colT_kernel(const float* __restrict_
 }
 
 static bool pack_tiled_ok(const void* a, const void* b, const void* c, const void* d) {
-  return (DAMC_X3_VARIANT & 8) == 0 &&  // the negblk limb order (launch_split_x3_conv)
-         (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16) == 0;
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16) == 0;
 }
 
 // 1 = layout not covered (the caller packs element-wise)
@@ -3542,7 +3065,7 @@ __global__ __launch_bounds__(256) void pack_conv_x3_lds_kernel(PackConvList l) {
 }
 
 bool pack_conv_x3_many_ok(const float* w, int cin, int k) {
-  return (DAMC_X3_VARIANT & 8) == 0 && k > 0 && k * k <= 32 && (uintptr_t)w % 16 == 0 && (cin % 128 == 0 || cin == 64);
+  return k > 0 && k * k <= 32 && (uintptr_t)w % 16 == 0 && (cin % 128 == 0 || cin == 64);
 }
 
 int pack_conv_x3_many_prep(PackConvList& l) {
@@ -3577,7 +3100,6 @@ int launch_pack_conv_x3_many(PackConvList l, hipStream_t s) {
 }
 
 int launch_pack_conv_x3(const float* w, int cout, int cin, int k, unsigned short* y, hipStream_t s) {
-  if ((DAMC_X3_VARIANT & 8) != 0) return DAMC_ERR_UNSUPPORTED;  // the channel-major walk needs the slice-major order
   if (cout <= 0 || cin % 8 != 0 || k <= 0 || (uintptr_t)y % 16 != 0) return DAMC_ERR_ARG;
   static const bool lds = [] {  // DAMC_PACK_CONV_LDS=0: the tap-group kernel below (A/B)
     const char* e = getenv("DAMC_PACK_CONV_LDS");
@@ -3634,7 +3156,7 @@ static void launch_x3_narrow_split(const GemmArgs& a0, hipStream_t s) {
   a.k_per_z = a.negk;
   a.proj_nostore = 0;
   const int ntm = (a.M + 63) / 64, ntn = (a.N + X3_BN - 1) / X3_BN;
-  hipLaunchKernelGGL((gemm_x3_kernel<EPI, O_DENSE, (DAMC_X3_VARIANT & ~(8 | 16)) | X3_NARROW>), dim3(ntm * ntn, 1, ks), dim3(512), 0, s,
+  hipLaunchKernelGGL((gemm_x3_kernel<EPI, O_DENSE, X3_BASE | X3_NARROW>), dim3(ntm * ntn, 1, ks), dim3(512), 0, s,
                      a);
   const long tot = (long)a.M * (a.N / 8);
   hipLaunchKernelGGL((x3_ksplit_reduce_kernel<EPI, O_DENSE>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a,
@@ -3658,7 +3180,7 @@ static int launch_gemm_x3(const GemmArgs& a, Epi epi, OMode om, int zdim, hipStr
   // the 4 x 4 conv walk (GemmArgs::kwalk): O_DENSE, 16 taps of whole 32-channel slices, the default / F32A tiles only
   if (a.kwalk && (!(om == O_DENSE && taps == 16 && a.kw == 4) && !(om == O_PHASE && taps == 4 && a.kw == 2)))
     return DAMC_ERR_ARG;
-  if (a.kwalk && (a.Cg % 32 != 0 || (DAMC_X3_VARIANT & ~0x105) != 0)) return DAMC_ERR_ARG;
+  if (a.kwalk && a.Cg % 32 != 0) return DAMC_ERR_ARG;
   if (((uintptr_t)a.A3 | (uintptr_t)a.A | (uintptr_t)a.B3 | (uintptr_t)a.C | (uintptr_t)a.C3 | (uintptr_t)a.mask) % 16 !=
       0)
     return DAMC_ERR_ARG;
@@ -3711,9 +3233,9 @@ static int launch_gemm_x3(const GemmArgs& a, Epi epi, OMode om, int zdim, hipStr
       c.proj_out = a.proj_out + b0 * (long)a.Hout * a.Wout * a.proj_np;
       if (c.a_f32) {  // the F32A tile: each 128-channel N tile projects its chunk
         if (a.N > PROJ_CHUNK && a.N % PROJ_CHUNK) return DAMC_ERR_UNSUPPORTED;
-        if (const int rc_ = launch_x3_t<EPI_BIAS_ACT, O_PHASE, DAMC_X3_VARIANT | X3_F32A>(c, zdim, s)) return rc_;
+        if (const int rc_ = launch_x3_t<EPI_BIAS_ACT, O_PHASE, X3_BASE | X3_F32A>(c, zdim, s)) return rc_;
       } else {  // the 128 x 256 layout: one N tile holding every channel
-        if (const int rc_ = launch_x3_t<EPI_BIAS_ACT, O_PHASE, DAMC_X3_VARIANT | 524288>(c, zdim, s)) return rc_;
+        if (const int rc_ = launch_x3_t<EPI_BIAS_ACT, O_PHASE, X3_BASE | X3_WIDE>(c, zdim, s)) return rc_;
       }
       continue;
     }
@@ -3753,23 +3275,23 @@ static int launch_gemm_x3(const GemmArgs& a, Epi epi, OMode om, int zdim, hipStr
     }
     if (epi == EPI_BIAS_ACT && om == O_DENSE && c.M <= 128 && !c.a_f32) {
       if (!(ew && ew[0] == '0')) {
-        if (const int rc_ = launch_x3_t<EPI_BIAS_ACT, O_DENSE, DAMC_X3_VARIANT | 524288>(c, zdim, s)) return rc_;
+        if (const int rc_ = launch_x3_t<EPI_BIAS_ACT, O_DENSE, X3_BASE | X3_WIDE>(c, zdim, s)) return rc_;
         continue;
       }
     }
     if (ew && ew[0] == '2' && !c.a_f32) {  // A/B only: every limb GEMM on the 128 x 256 layout (bitwise the default)
       if (epi == EPI_BIAS_ACT && om == O_PHASE) {
-        if (const int rc_ = launch_x3_t<EPI_BIAS_ACT, O_PHASE, DAMC_X3_VARIANT | 524288>(c, zdim, s)) return rc_;
+        if (const int rc_ = launch_x3_t<EPI_BIAS_ACT, O_PHASE, X3_BASE | X3_WIDE>(c, zdim, s)) return rc_;
         continue;
       }
       if (epi == EPI_MASK && om == O_DENSE) {
-        if (const int rc_ = launch_x3_t<EPI_MASK, O_DENSE, DAMC_X3_VARIANT | 524288>(c, zdim, s)) return rc_;
+        if (const int rc_ = launch_x3_t<EPI_MASK, O_DENSE, X3_BASE | X3_WIDE>(c, zdim, s)) return rc_;
         continue;
       }
     }
 #define DAMC_X3(E_, O_)                                                      \
   if (epi == E_ && om == O_) {                                               \
-    const int rc_ = c.a_f32 ? launch_x3_t<E_, O_, DAMC_X3_VARIANT | X3_F32A>(c, zdim, s) \
+    const int rc_ = c.a_f32 ? launch_x3_t<E_, O_, X3_BASE | X3_F32A>(c, zdim, s) \
                             : launch_x3_t<E_, O_>(c, zdim, s);               \
     if (rc_) return rc_;                                                     \
     continue;                                                                \
@@ -3796,10 +3318,9 @@ int launch_wgrad_x3(const GemmArgs& a, int slices, const char* prof_name, double
   if (a.N % 8 != 0 || a.ldc % 8 != 0 || a.ldc < a.N || a.c_zstride < (long)a.M * a.ldc) return DAMC_ERR_ARG;
   if (((uintptr_t)a.A3 | (uintptr_t)a.B3 | (uintptr_t)a.C) % 16 != 0) return DAMC_ERR_ARG;
   if ((double)a.Cg * a.K * 6 >= 2147483647.0 || (double)a.N * a.K * 6 >= 2147483647.0) return DAMC_ERR_UNSUPPORTED;
-  constexpr int BM = (DAMC_X3_VARIANT & 524288) ? 128 : X3_BM, BN = (DAMC_X3_VARIANT & 524288) ? 256 : X3_BN;
-  const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
+  const int ntm = (a.M + X3_BM - 1) / X3_BM, ntn = (a.N + X3_BN - 1) / X3_BN;
   ProfScope ps(prof_name, flops, s);
-  hipLaunchKernelGGL((gemm_x3_kernel<EPI_STORE, O_WGRAD>), dim3(ntm * ntn, 1, a.wg_phases * slices), dim3(512), 0, s,
+  hipLaunchKernelGGL((gemm_x3_kernel<EPI_STORE, O_WGRAD, X3_BASE>),dim3(ntm * ntn, 1, a.wg_phases * slices), dim3(512), 0, s,
                      a);
   return (int)hipGetLastError();
 }

@@ -59,7 +59,6 @@ struct Shape {
   unsigned short* a3 = nullptr;  // limb-engine operands (x3 layout)
   unsigned short* b3 = nullptr;
   unsigned short* b3n = nullptr;  // the same with odd X3_NEGK-blocks negated (GemmArgs::b_negblk)
-  unsigned short* b3c = nullptr;  // slice-major (channel-major K walk, V & 8) with sign blocks
 };
 
 static unsigned short* split_dev(const float* d, size_t n) {
@@ -77,8 +76,8 @@ template <int V, int NEG = 0>
 static void run_x3(const Shape& sh, hipStream_t s) {
   GemmArgs a = sh.a;
   a.A3 = sh.a3;
-  a.B3 = (V & 8) ? sh.b3c : (NEG ? sh.b3n : sh.b3);
-  a.b_negblk = (V & 8) ? 1 : NEG;
+  a.B3 = NEG ? sh.b3n : sh.b3;
+  a.b_negblk = NEG;
   a.b_zstride = (long)a.N * a.K;
   if (sh.phase)
     launch_x3_t<EPI_BIAS_ACT, O_PHASE, V>(a, 4, s);
@@ -241,11 +240,6 @@ int main(int argc, char** argv) {
     sh.b3 = split_dev(sh.bt, (size_t)(sh.phase ? 4 : 1) * a.N * a.K);
     const size_t nb = (size_t)(sh.phase ? 4 : 1) * a.N * a.K;
     CK(hipMalloc(&sh.b3n, nb * 6));
-    CK(hipMalloc(&sh.b3c, nb * 6));
-    if (launch_split_x3_cmaj(sh.bt, (long)nb, a.K, a.Cg, 32, sh.b3c, 0) != 0) {
-      printf("split failed\n");
-      exit(1);
-    }
     if (launch_split_x3_negblk(sh.bt, (long)nb, a.K, sh.b3n, 0) != 0) {
       printf("split failed\n");
       exit(1);
@@ -297,13 +291,13 @@ int main(int argc, char** argv) {
         }
         if (sh.phase) {
           a.sgn = sg;
-          if (f32a) launch_x3_t<EPI_BIAS_ACT, O_PHASE, 261 | X3_F32A>(a, 4, s);
-          else launch_x3_t<EPI_BIAS_ACT, O_PHASE, 261>(a, 4, s);
+          if (f32a) launch_x3_t<EPI_BIAS_ACT, O_PHASE, X3_BASE | X3_F32A>(a, 4, s);
+          else launch_x3_t<EPI_BIAS_ACT, O_PHASE, X3_BASE>(a, 4, s);
         } else {
           a.mask = nullptr;
           a.mask_sgn = dbits;
-          if (f32a) launch_x3_t<EPI_MASK, O_DENSE, 261 | X3_F32A>(a, 1, s);
-          else launch_x3_t<EPI_MASK, O_DENSE, 261>(a, 1, s);
+          if (f32a) launch_x3_t<EPI_MASK, O_DENSE, X3_BASE | X3_F32A>(a, 1, s);
+          else launch_x3_t<EPI_MASK, O_DENSE, X3_BASE>(a, 1, s);
         }
         CK(hipStreamSynchronize(s));
         outs[v] = to_host(c, nout);
@@ -343,9 +337,7 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  // timing probes beside the default: 512 = no DMA after the first tile, 1024 = fragment reads of the first tile only,
-  // 4096 = DMA from one L2-hot 64 KB window
-  V vars[] = {{"v261", run_x3<261, 1>}, {"f32a", run_x3<261 | X3_F32A, 1>}, {"wide", run_x3<261 | 524288, 1>}};
+  V vars[] = {{"v261", run_x3<X3_BASE, 1>}, {"f32a", run_x3<X3_BASE | X3_F32A, 1>}, {"wide", run_x3<X3_BASE | X3_WIDE, 1>}};
   const int NV = sizeof(vars) / sizeof(vars[0]);
   // accuracy against an fp64 reference on sampled outputs (normalised by sum |a b|)
   {
@@ -446,8 +438,8 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&c2, (size_t)B * NP * 4));
     GemmArgs a2 = a;
     a2.C = c2;
-    launch_x3_t<EPI_BIAS_ACT, O_DENSE, 261>(a, 1, s);
-    launch_x3_t<EPI_BIAS_ACT, O_DENSE, 261 | 524288>(a2, 1, s);
+    launch_x3_t<EPI_BIAS_ACT, O_DENSE, X3_BASE>(a, 1, s);
+    launch_x3_t<EPI_BIAS_ACT, O_DENSE, X3_BASE | X3_WIDE>(a2, 1, s);
     CK(hipStreamSynchronize(s));
     std::vector<float> r1 = to_host(o1, (size_t)B * NP), r2 = to_host(c2, (size_t)B * NP);
     printf("proj fwd x3: wide bitwise default: %s\n", memcmp(r1.data(), r2.data(), r1.size() * 4) ? "NO" : "yes");
@@ -456,8 +448,8 @@ int main(int argc, char** argv) {
       for (int v = 0; v < 2; ++v) {
         CK(hipEventRecord(e0, s));
         for (int k = 0; k < reps; ++k) {
-          if (v == 0) launch_x3_t<EPI_BIAS_ACT, O_DENSE, 261>(a, 1, s);
-          else launch_x3_t<EPI_BIAS_ACT, O_DENSE, 261 | 524288>(a, 1, s);
+          if (v == 0) launch_x3_t<EPI_BIAS_ACT, O_DENSE, X3_BASE>(a, 1, s);
+          else launch_x3_t<EPI_BIAS_ACT, O_DENSE, X3_BASE | X3_WIDE>(a, 1, s);
         }
         CK(hipEventRecord(e1, s));
         CK(hipEventSynchronize(e1));
