@@ -328,21 +328,15 @@ __device__ __forceinline__ void st_global(float* p, float v) { *(__attribute__((
 // are copied into that workgroup's LDS once, in MFMA fragment order (one ds_read_b128 per lane and k-group, no
 // bank conflicts).  toff_j staggers the blocks' first tiles so the LDS load is even across slots (106.5 KB per
 // workgroup at the CIFAR defaults, nf 4).
-// Per stage (block j of step k, s = 7 k + j) a workgroup waits until every slot of its team has published stage
-// s - 1, reads its row tile's block input, runs 16 x 16 v_mfma_f32_16x16x4_f32 tiles over K split in quarters by
-// its 4 waves, and publishes its 16 x 8 outputs.  A block whose input is cat(prev, skip) takes the skip half
-// (complete stages earlier) and its MFMAs BEFORE the wait, and only the prev half after it.
-// Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility, first row of the sc1 table): every handed-off value
-// is stored sc1 and every storing wave drains vmcnt before the workgroup barrier, then ONE lane stores the
-// slot's flag (= stages done) sc1; a consumer's wave 0 polls its team's T flags with sc1 loads, the other waves
-// join it at a barrier, and every load of handed-off bytes is an sc1 load.  Outputs and z go to per-step ring
+// Per stage (block j of step k, s = 7 k + j) a workgroup reads its row tile's block input, runs 16 x 16
+// v_mfma_f32_16x16x4_f32 tiles over K split in quarters by its 4 waves (one per SIMD), and stores its 16 x 8 outputs.
+// A block whose input is cat(prev, skip) takes the skip half (complete stages earlier) and its MFMAs first, and only
+// then the prev half.
+// Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility): data-driven, see "Sentinel hand-offs" below.  Every
+// handed-off value is stored sc1 and every load of handed-off bytes is an sc1 load.  Outputs and z go to per-step ring
 // slots, so no address is ever rewritten within a sweep.  Every wait is bounded: past the budget (or once any
 // workgroup has failed) the workgroup records the failure in the error word and leaves, so the grid drains, and
-// the copy-out writes NaN into zt.
-// waves 0-3 compute (K in quarters), wave 4 polls, wave 5 stores the slot's flag: a poll issued behind the same
-// wave's flag store would return only after that store's write-through ack (loads and stores share vmcnt, in order)
-constexpr int TS_THREADS = 384;
-constexpr int TS_PUB = 320;  // the publishing lane
+// team_finish_kernel recomputes the sweep.
 constexpr int TS_MAXT = 64;     // slots per team (CUs per XCD)
 constexpr int TS_TAB_STEPS = 256;  // steps whose schedule rows are kept in LDS
 
@@ -369,17 +363,13 @@ struct TsArgs {
   float* zring;       // (n+1, B, nz): z before step k at zring + k * B * nz
   const float* tab;   // (n, 8): c0..c4, is_last, noisy_k
   const SweepCall* call;
-  unsigned* flags;    // [8][TS_MAXT][TS_FS]: stages published by (team, slot)
-  int* err;
-  int* diag;          // [P][4]: a failed wait's {stage needed, flag of the first late slot, late-slot mask lo, hi}
-  int sent;           // 1: sentinel hand-offs (TS_SENT): no drain before the flag, every handed-off load re-read until
-                      // it holds no sentinel; 0: the drained-flag protocol (DAMC_SWEEP_SENT=0, read per call)
+  int* err;           // the error word: set by a wait that gave up (or DAMC_SWEEP_FORCE_FAIL), read by team_finish_kernel
   long budget;        // wait budget in 100 MHz ticks
   int wlds;           // weight LDS floats per workgroup (host maximum over slots)
   int fast;           // 128 / 100: sweep_fast_kernel<fast, 128> (the shapes compiled in; DAMC_SWEEP_FAST=0: off)
-  uint64_t* trace;    // tools only (DAMC_SWEEP_TRACE): [P][7n][4] 100 MHz stamps {wait begin (sent 2: task start),
-                      // wait end, reduced, published}
-  int dbg;            // timing experiments only (DAMC_SWEEP_DBG, wrong results): 1 no drain before the flag,
+  uint64_t* trace;    // tools only (DAMC_SWEEP_TRACE): [P][7n][4] 100 MHz stamps {task start, wake (the
+                      // previous block's half is read from here on), reduced, published (the stage's stores issued)}
+  int dbg;            // timing experiments only (DAMC_SWEEP_DBG, wrong results):
                       // 2 no payload loads, 4 no MFMA, 8 no epilogue operand loads, 16 no output stores,
                       // 32 no zB / sin / cos (in0), 64 no z loads (in0); tests: 4096 every workgroup reports a
                       // failed wait at once (exercises the rescue in team_finish_kernel)
@@ -392,54 +382,11 @@ __device__ __forceinline__ int ts_tiles(const TsBlock& b, int T, int t, int* tn0
   return f < b.ntn ? (b.ntn - f + T - 1) / T : 0;
 }
 
-// wave 4 (which issues no other loads, so nothing queues in front of its poll) polls the T flags of the team (one
-// 128-B line each: a shared line would serialise the producers' stores and the pollers' loads on one memory
-// channel) until all have published `need` stages; every thread returns whether the wait succeeded (a barrier is
-// inside).  One poll in flight: three staggered ones measured 4-5 % slower per sweep.
-constexpr int TS_FS = 32;  // flag stride, unsigned
-__device__ __forceinline__ bool ts_wait(const unsigned* fl, int T, unsigned need, int* err, long budget, int* sflag,
-                                        int* diag) {
-  if (threadIdx.x >= 256 && threadIdx.x < 320) {
-    const int lane = threadIdx.x - 256;
-    int ok = 1;
-    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-    for (unsigned it = 0;; ++it) {
-      const unsigned v =
-          lane < T ? __hip_atomic_load(fl + lane * TS_FS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : need;
-      if (__all(v >= need)) break;
-      __builtin_amdgcn_s_sleep(1);
-      if ((it & 63) == 63) {
-        const int e = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (e || (long)(__builtin_amdgcn_s_memrealtime() - t0) > budget) {
-          if (!e && lane == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          // diagnostics: which slots of the team had not published `need` stages when this wait gave up
-          const uint64_t late = __ballot(v < need);
-          const int first = late ? __builtin_ctzll(late) : 0;
-          const unsigned vf = __shfl(v, first);
-          if (lane == 0) {
-            int* dg = diag + blockIdx.x * 4;
-            dg[0] = (int)need;
-            dg[1] = e ? -1 : (int)vf;  // -1: gave up because another workgroup had failed
-            dg[2] = (int)(unsigned)late;
-            dg[3] = (int)(unsigned)(late >> 32);
-          }
-          ok = 0;
-          break;
-        }
-      }
-    }
-    if (lane == 0) *sflag = ok;
-  }
-  __syncthreads();
-  return *sflag != 0;
-}
-
 // Sentinel hand-offs.  Every ring slot (block outputs and z of every step) is written exactly once per sweep, and
 // the setup kernel fills all of them with a NaN bit pattern no arithmetic produces (hardware NaNs are canonical,
 // 0x7FC00000) before the launch.  A handed-off 4-B value is then either the sentinel or final (aligned 4-B stores
-// do not tear), so the producer publishes its flag right behind its stores without draining them (one memory round
-// trip less per stage), and a consumer that has seen the flag re-reads (sc1) any load group that still holds a
-// sentinel.  The flag stays the cheap "probably ready" signal; the data itself proves readiness.
+// do not tear), so a producer just stores, without a drain or a flag, and a consumer re-reads (sc1) any load group that
+// still holds a sentinel: the data itself proves readiness.
 // The caller data that enters the ring unchanged is z; the setup kernel stores its NaNs canonical.  The other ring
 // values are computed, and a VALU op may carry a (quieted) input NaN's payload through, so a weight or xemb holding
 // exactly the TS_SENT pattern could still reach the ring.  Then the consumers' bounded wait expires (20 ms),
@@ -473,7 +420,7 @@ __device__ __forceinline__ bool any_sent(const f32x4 (&x)[N]) {
 template <bool EMB>
 __device__ __forceinline__ void ts_half(f32x4& acc, const float* wl, int kps, const __amdgpu_buffer_rsrc_t& rs,
                                         long soff, int wsrc, int row, bool rok, const float* embs, int ld, int dbg,
-                                        int sent = 0, int* err = nullptr, long budget = 0) {
+                                        int* err = nullptr, long budget = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = lane & 15, q = lane >> 4;
   const int kq = kps >> 2, ng = kq >> 4, kbase = wave * kq;
@@ -493,7 +440,7 @@ __device__ __forceinline__ void ts_half(f32x4& acc, const float* wl, int kps, co
       }
     };
     load();
-    if (!EMB && sent) {  // sentinel hand-off (see TS_SENT): re-read the chunk until it holds no sentinel
+    if (!EMB) {  // sentinel hand-off (see TS_SENT): re-read the chunk until it holds no sentinel
       bool bad = false;
 #pragma unroll
       for (int c = 0; c < CH_CHUNK; ++c)
@@ -583,14 +530,10 @@ __device__ __forceinline__ void ts_ready(f32x4 (&x)[N], int kps, const __amdgpu_
   } while (__any(any_sent(x)));
 }
 
-// NT: threads per workgroup.  The flag protocols (sent 0 / 1) need the poll wave (threads 256..319) and the flag
-// lane (TS_PUB): 384.  The data-driven hand-off (sent 2, the default) has neither, so it runs 4 waves, one per SIMD,
-// which lifts the register cap from 256 to 512 per lane: at 384 threads the kernel spilled 38 VGPRs to scratch (152 B
-// per lane) once the sentinel re-read paths were added, +17 % sweep time (round 4 A/B).
-template <int NT>
-__global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
+// 4 waves, one per SIMD, so a lane may hold 512 registers: the kernel needs 243 VGPRs + 12 AGPRs and spilled at six
+// waves
+__global__ __launch_bounds__(256) void sweep_team_kernel(TsArgs a) {
   __shared__ __attribute__((aligned(16))) float red[4][TM][16];
-  __shared__ int sflag;
   __shared__ uint64_t trs[3];                    // tools only: this stage's stamps
   __shared__ float tabs[8 * TS_TAB_STEPS];       // the step table (n <= TS_TAB_STEPS)
   __shared__ int lbase[7];                       // LDS float offset of block j's first owned tile
@@ -601,20 +544,17 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
   const int er = tid >> 3, ec = tid & 7;
   const int T = a.T, team = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int nz = a.nz, B = a.B, G = a.G;
-  const int sent = NT == 256 ? 2 : a.sent;  // compile-time in the 4-wave (data-driven) instantiation
-  if (team >= G || slot >= T) return;  // no row tile for this team (its flags are never waited on)
+  if (team >= G || slot >= T) return;  // no row tile for this team
   if (a.dbg & 4096) {  // tests only: report a failed wait at once
     if (tid == 0) __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
   }
   const int nrt = (G - team + 7) / 8;  // row tiles of the team: team + 8 i
-  unsigned* const myflag = a.flags + (team * TS_MAXT + slot) * TS_FS;
-  const unsigned* const teamflags = a.flags + team * TS_MAXT * TS_FS;
   float* const embs = lds + a.wlds;
   const int ld0 = emb_ld(a.b[0].kpa);
 
   if (a.n <= TS_TAB_STEPS)
-    for (int i = tid; i < 8 * a.n; i += NT) tabs[i] = a.tab[i];
+    for (int i = tid; i < 8 * a.n; i += 256) tabs[i] = a.tab[i];
   // ---- the owned weight tiles into LDS, fragment order: (half, wave, k-group, lane) -> f32x4
   if (tid == 0) {
     int off = 0;
@@ -640,7 +580,7 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
         const int ng = kps >> 6;  // k-groups per wave
         const int units = 4 * ng * 64;
         f32x4* d4 = reinterpret_cast<f32x4*>(dst + (h ? 16 * b.kpa : 0));
-        for (int u = tid; u < units; u += NT) {
+        for (int u = tid; u < units; u += 256) {
           const int l = u & 63, g = (u >> 6) % ng, w = (u >> 6) / ng;
           const int mm = l & 15, qq = l >> 4;
           const int k = w * (kps >> 2) + 16 * g + 4 * qq;
@@ -663,7 +603,6 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
   const int eps_log_steps = call->eps_log_steps;
   const uint64_t seed = call->seed, chain_base = call->chain_base, step_offset = call->step_offset;
   const long ring_bytes = a.ring_step * 4;
-  unsigned known = 0;  // stages known complete team-wide (the last wait's target)
   const bool cw = wave < 4;  // compute wave
   // in0: wave w's B^T column tile (columns 16 w .. 16 w + 15 of zB), in registers for the whole sweep
   f32x4 bv[EMB_G];
@@ -705,25 +644,15 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
       // the slot's tiles of block j from the prologue's table (two integer divisions per task otherwise)
       const int nt = __builtin_amdgcn_readfirstlane(tinfo[j][0]);
       const int tn0 = __builtin_amdgcn_readfirstlane(tinfo[j][1]);
-      // tools only: the poll wave keeps its stamps in LDS (a global store in front of its poll would delay it);
-      // the publishing lane writes them out after the flag
-      const bool tr = a.trace != nullptr && tid == (NT > 256 ? 256 : 0);
-      if (nt == 0) {  // nothing to compute: publish at once (this slot's earlier stores are drained)
-        if (tid == TS_PUB && sent < 2) __hip_atomic_store(myflag, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        continue;
-      }
-      // tools: with the data-driven hand-off there is no flag wait, so the first stamp marks the task's start instead
-      if (tr && sent == 2) trs[0] = __builtin_amdgcn_s_memrealtime();
+      // tools only: thread 0 keeps the stage's stamps in LDS and writes them out after the stage
+      const bool tr = a.trace != nullptr && tid == 0;
+      if (nt == 0) continue;  // nothing to compute
+      if (tr) trs[0] = __builtin_amdgcn_s_memrealtime();  // the task's start
       const bool final_ = j == 6;
       const float* wbase = lds + lbase[j];
       // a skip half (produced at stage sb = 7 k + srcB, two or more stages back) always goes first, so every slot sums
-      // in the same order (team_finish_kernel's rescue relies on it); it is normally known complete already (sb <
-      // known); a slot that owned no tile of the stages since waits for it here
+      // in the same order (team_finish_kernel's rescue relies on it)
       const bool skip_early = b.kpb > 0;
-      if (skip_early && sent < 2 && !(7u * k + b.srcB < known)) {
-        if (!ts_wait(teamflags, T, 7u * k + b.srcB + 1, a.err, a.budget, &sflag, a.diag)) return;
-        known = 7u * k + b.srcB + 1;
-      }
       bool waited = false;
 #pragma unroll 1
       for (int rt = 0; rt < nrt; ++rt) {
@@ -770,21 +699,18 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
           if (pre && cw) ts_load<CH_CHUNK>(xs, b.kpb, rr, a.b[b.srcB].ooff, b.wb, xrow, xok);
           if (skip_early && !pre && cw)
             ts_half<false>(acc, wl + 16 * b.kpa, b.kpb, rr, a.b[b.srcB].ooff, b.wb, xrow, xok, nullptr, 0, a.dbg,
-                           sent, a.err, a.budget);
+                           a.err, a.budget);
           const int half = nz >> 1;
 
-          // ---- wait for stage s - 1 of the team (once per stage)
+          // tools: the stage's "wake" stamp (once per stage)
           if (!waited) {
-            if (tr && sent < 2) trs[0] = __builtin_amdgcn_s_memrealtime();
-            if (s > 0 && sent < 2 && !ts_wait(teamflags, T, s, a.err, a.budget, &sflag, a.diag)) return;
             if (tr) trs[1] = __builtin_amdgcn_s_memrealtime();
-            known = s;
             waited = true;
           }
 
           if (j == 0) {  // in0: [sin 2pi zB, cos 2pi zB, z] of the 16 rows into LDS (as chain_kernel<true>)
             load_z();
-            if (sent && cw && __any(any_sent(zv4))) {  // z of this step not landed yet: re-read (bounded)
+            if (cw && __any(any_sent(zv4))) {  // z of this step not landed yet: re-read (bounded)
               const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
               unsigned it = 0;
               do {
@@ -818,20 +744,19 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
                   if (kk < nz) embs[m * ld0 + 2 * half + kk] = zv4[g][e];
                 }
             }
-            for (int c = 2 * half + nz + tid; c < b.kpa; c += NT)
+            for (int c = 2 * half + nz + tid; c < b.kpa; c += 256)
 #pragma unroll
               for (int r = 0; r < TM; ++r) embs[r * ld0 + c] = 0.f;
             __syncthreads();
             if (cw) ts_half<true>(acc, wl, b.kpa, rr, 0, 0, xrow, xok, embs, ld0, a.dbg);
           } else if (cw && pre) {
             ts_load<CH_CHUNK>(xa, b.kpa, rr, a.b[b.srcA].ooff, b.wa, xrow, xok);
-            if (sent) ts_ready<CH_CHUNK>(xs, b.kpb, rr, a.b[b.srcB].ooff, b.wb, xrow, xok, a.err, a.budget);
+            ts_ready<CH_CHUNK>(xs, b.kpb, rr, a.b[b.srcB].ooff, b.wb, xrow, xok, a.err, a.budget);
             ts_mfma<CH_CHUNK>(acc, wl + 16 * b.kpa, b.kpb, xs, a.dbg);
-            if (sent) ts_ready<CH_CHUNK>(xa, b.kpa, rr, a.b[b.srcA].ooff, b.wa, xrow, xok, a.err, a.budget);
+            ts_ready<CH_CHUNK>(xa, b.kpa, rr, a.b[b.srcA].ooff, b.wa, xrow, xok, a.err, a.budget);
             ts_mfma<CH_CHUNK>(acc, wl, b.kpa, xa, a.dbg);
           } else if (cw) {
-            ts_half<false>(acc, wl, b.kpa, rr, a.b[b.srcA].ooff, b.wa, xrow, xok, nullptr, 0, a.dbg, sent, a.err,
-                           a.budget);
+            ts_half<false>(acc, wl, b.kpa, rr, a.b[b.srcA].ooff, b.wa, xrow, xok, nullptr, 0, a.dbg, a.err, a.budget);
           }
           if (cw) {
 #pragma unroll
@@ -853,7 +778,7 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
             } else {  // reverse step (diffusion_net.py:601-620): eps = z + out; pred = c0 (z - eps c1)
               const long zi = (long)erow * nz + ecol;
               float zv = ld_sc1_f(zk + zi);
-              if (sent && is_sent(zv)) {  // this thread's own store of the previous step, not landed yet
+              if (is_sent(zv)) {  // this thread's own store of the previous step, not landed yet
                 const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
                 unsigned it = 0;
                 do {
@@ -878,11 +803,8 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
           __syncthreads();  // red (and the in0 image) are reused by the next task
         }
       }
-      // publish: (drained-flag protocol) every storing wave drains first; one lane then stores the slot's flag
-      if (!sent && !(a.dbg & 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (tid == TS_PUB && sent < 2) __hip_atomic_store(myflag, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.trace && tid == (NT > 256 ? TS_PUB : 0)) {
+      if (a.trace && tid == 0) {
         uint64_t* tg = a.trace + ((long)blockIdx.x * 7 * a.n + s) * 4;
         tg[0] = trs[0];
         tg[1] = trs[1];
@@ -905,7 +827,7 @@ __global__ __launch_bounds__(NT) void sweep_team_kernel(TsArgs a) {
 //     covers the rest of the setup and every wait counts its loads exactly;
 //   * double-buffers the wave-partial LDS tile, so one barrier per task goes (the next task writes the other buffer;
 //     a wave reaches that task's barrier only after its epilogue reads of this one).
-// Arithmetic, fragment order and MFMA order are sweep_team_kernel's (sent 2), so team_finish_kernel's rescue and the
+// Arithmetic, fragment order and MFMA order are sweep_team_kernel's, so team_finish_kernel's rescue and the
 // tests' bitwise gates hold unchanged.
 constexpr int fs_dout(int j, int nz, int w) { return j == 0 ? w : (j <= 4 ? 2 * w : (j == 5 ? w : nz)); }
 constexpr int fs_srcb(int j) { return j == 4 ? 2 : (j == 5 ? 1 : (j == 6 ? 0 : -1)); }
@@ -1631,7 +1553,7 @@ __global__ void transpose_kernel(const float* in, int rows, int cols, float* out
   out[c * rows + r] = in[i];
 }
 
-// the call's per-call record and z, and (team launch) the team flags, error word and diagnostics zeroed: a kernel in
+// the call's per-call record and z, and (team launch) the error word zeroed: a kernel in
 // the stream, not a memset node, so a captured sweep orders it like every other kernel
 __global__ void sweep_setup_kernel(SweepCall c, SweepCall* dst, const float* zt, float* zw, long n, unsigned* zero,
                                    long nzero, f32x4* s1, long ns1, f32x4* s2, long ns2) {
@@ -1669,14 +1591,11 @@ struct SweepWs {
   float *px, *qt, *t1, *t2, *xs, *cx, *gh, *z;
   float* outs[7];
   SweepCall* call;
-  // team sweep: per-step ring slots of the block outputs and of z, the step table, the team flags, the error word
+  // team sweep: per-step ring slots of the block outputs and of z, the step table, the error word
   float *ring, *zring, *tab;
-  unsigned* tflags;
   int* err;
-  int* diag;
   size_t bytes;
 };
-constexpr long TS_CTL_WORDS = 8L * TS_MAXT * TS_FS + 64 + 8L * TS_MAXT * 4;
 
 size_t carve(const damc_denoiser_t* d, int B, int n, char* base, SweepWs* w) {
   size_t off = 0;
@@ -1715,10 +1634,7 @@ size_t carve(const damc_denoiser_t* d, int B, int n, char* base, SweepWs* w) {
   t.ring = take((long)n * B * S);
   t.zring = take((long)(n + 1) * B * d->nz);
   t.tab = take(8L * n);
-  // team flags, then the error word, then the failed waits' diagnostics
-  t.tflags = reinterpret_cast<unsigned*>(take(TS_CTL_WORDS));
-  t.err = reinterpret_cast<int*>(t.tflags + 8 * TS_MAXT * TS_FS);
-  t.diag = reinterpret_cast<int*>(t.tflags + 8 * TS_MAXT * TS_FS + 64);
+  t.err = reinterpret_cast<int*>(take(1));
   t.bytes = off;
   if (w) *w = t;
   return off;
@@ -1954,9 +1870,7 @@ int team_slots() {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
     cached[dev] = (cus % 8 == 0 && cus >= 8) ? std::min(cus / 8, TS_MAXT) : -1;
-    (void)hipFuncSetAttribute((const void*)sweep_team_kernel<TS_THREADS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)TS_LDS_MAX);
-    (void)hipFuncSetAttribute((const void*)sweep_team_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)sweep_team_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)TS_LDS_MAX);
     (void)hipFuncSetAttribute((const void*)sweep_fast_kernel<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)TS_LDS_MAX);
@@ -2029,12 +1943,9 @@ int team_plan(const damc_denoiser_t* d, const SweepWs& w, int B, int n, TsArgs* 
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return DAMC_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(mu);
     if (ok_sm[dev] != sm) {
-      int per = 0;
       int per2 = 0;
       int per4 = 0, per5 = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, sweep_team_kernel<TS_THREADS>, TS_THREADS, sm) !=
-              hipSuccess || per < 1 ||
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per2, sweep_team_kernel<256>, 256, sm) != hipSuccess ||
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per2, sweep_team_kernel, 256, sm) != hipSuccess ||
           per2 < 1 ||
           hipOccupancyMaxActiveBlocksPerMultiprocessor(&per4, sweep_fast_kernel<128, 128>, 256, sm) != hipSuccess ||
           per4 < 1 ||
@@ -2058,9 +1969,7 @@ int team_plan(const damc_denoiser_t* d, const SweepWs& w, int B, int n, TsArgs* 
   a->zring = w.zring;
   a->tab = w.tab;
   a->call = w.call;
-  a->flags = w.tflags;
   a->err = w.err;
-  a->diag = w.diag;
   a->budget = 2000000;  // 20 ms at 100 MHz per wait: a stage takes microseconds
   a->wlds = (int)wl;
   // the shape-specialised kernel: only where every block matches the compiled-in table
@@ -2146,14 +2055,12 @@ int run_chain_team(TsArgs& a, int P, size_t smem, const float* coef, hipStream_t
     DAMC_CHECK(hipMalloc(&a.trace, tbytes));
     DAMC_CHECK(hipMemsetAsync(a.trace, 0, tbytes, s));
   }
-  if (a.sent == 2 && a.fast == 128)
+  if (a.fast == 128)
     hipLaunchKernelGGL((sweep_fast_kernel<128, 128>), dim3(P), dim3(256), smem, s, a);
-  else if (a.sent == 2 && a.fast == 100)
+  else if (a.fast == 100)
     hipLaunchKernelGGL((sweep_fast_kernel<100, 128>), dim3(P), dim3(256), smem, s, a);
-  else if (a.sent == 2)
-    hipLaunchKernelGGL((sweep_team_kernel<256>), dim3(P), dim3(256), smem, s, a);
   else
-    hipLaunchKernelGGL((sweep_team_kernel<TS_THREADS>), dim3(P), dim3(TS_THREADS), smem, s, a);
+    hipLaunchKernelGGL(sweep_team_kernel, dim3(P), dim3(256), smem, s, a);
   DAMC_LAUNCH_CHECK();
   if (trace) {  // tools/sweep_trace.py reads the dump: P, n, G, then the stamps
     std::vector<uint64_t> h((size_t)P * 7 * n * 4);
@@ -2378,18 +2285,6 @@ extern "C" long damc_sweep_team_failures(int device) {
   (void)team_healthy(device);  // picks up a failure that has completed since the last sweep
   std::lock_guard<std::mutex> lk(g_health_mu);
   return g_health[device].failures;
-}
-
-extern "C" int damc_sweep_team_words(const damc_denoiser_t* d, int B, int n, const void* wsp, size_t wsb, int* out,
-                                     int nwords) {
-  if (validate(d) || B <= 0 || n <= 0 || !wsp || !out || nwords <= 0) return DAMC_ERR_ARG;
-  if (wsb < carve(d, B, n, nullptr, nullptr)) return DAMC_ERR_WORKSPACE;
-  SweepWs w;
-  carve(d, B, n, reinterpret_cast<char*>(const_cast<void*>(wsp)), &w);
-  const long cnt = std::min<long>(nwords, TS_CTL_WORDS);
-  DAMC_CHECK(hipDeviceSynchronize());
-  DAMC_CHECK(hipMemcpy(out, w.tflags, cnt * sizeof(int), hipMemcpyDeviceToHost));
-  return 0;
 }
 
 extern "C" size_t damc_sweep_workspace_bytes(const damc_denoiser_t* d, int B, int n) {
@@ -2659,27 +2554,18 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   int dev = 0;
   DAMC_CHECK(hipGetDevice(&dev));
   // inside a caller's capture the team launch is recorded like any kernel (DAMC_SWEEP_CAPTURE_TEAM=0, read per
-  // call: the launch chain instead).  Round 2 recorded the launch chain there because a replayed team launch timed
-  // out: its flags were zeroed by a hipMemsetAsync node, which the replay did not order before the team kernel
-  // (DAMC_SWEEP_MEMSET_FLAGS=1 restores that form for tools/diag_team_capture.py); the setup kernel zeroes them now.
+  // call: the launch chain instead).  What the team kernel needs zeroed or filled, the setup kernel writes: a kernel
+  // is ordered before it in a replay as in the stream (a memset node was not: DESIGN.md §1).
   const char* tic = getenv("DAMC_SWEEP_CAPTURE_TEAM");
   const bool team_in_capture = !(tic && tic[0] == '0');
   const bool team = (!capturing || team_in_capture) && team_enabled() && dev < 64 && team_healthy(dev) &&
                     team_plan(d, w, B, n, &ta, &tP, &tsm) == 0;
   int* health = team ? team_health_word(dev, capturing) : nullptr;
-  const char* mf = getenv("DAMC_SWEEP_MEMSET_FLAGS");  // diagnosis only: round 2's memset form (see above)
-  const bool memset_flags = team && mf && mf[0] == '1';
-  if (memset_flags) DAMC_CHECK(hipMemsetAsync(w.tflags, 0, TS_CTL_WORDS * sizeof(unsigned), s));
-  const long nzero = (team && !memset_flags) ? TS_CTL_WORDS : 0;
-  // hand-off protocol (read per call): 2 (default) data-driven sentinel hand-offs, no flags; 1 flags without drain +
-  // sentinel checks; 0 drained flags.  Bitwise the same results; same-box A/B at B=128 (tools/sweep_ab.py): 2 is
-  // 6-7 % faster than 0, 1 is 4-5 % slower than 0
-  const char* se = getenv("DAMC_SWEEP_SENT");
-  if (team) ta.sent = se ? atoi(se) : 2;
-  const long ns1 = (team && ta.sent) ? (long)n * B * S / 4 : 0, ns2 = (team && ta.sent) ? (long)n * nzb / 4 : 0;
+  // the data-driven hand-off's sentinels: every ring slot of the sweep (TS_SENT)
+  const long nzero = team ? 1 : 0, ns1 = team ? (long)n * B * S / 4 : 0, ns2 = team ? (long)n * nzb / 4 : 0;
   const long sgrid = std::min<long>(std::max<long>(std::max(nzb, nzero), (ns1 + ns2) / 8), 1L << 16);
   hipLaunchKernelGGL(sweep_setup_kernel, dim3((unsigned)((sgrid + 255) / 256)), dim3(256), 0, s, call, w.call, zt,
-                     team ? w.zring : w.z, nzb, w.tflags, nzero, reinterpret_cast<f32x4*>(w.ring), ns1,
+                     team ? w.zring : w.z, nzb, reinterpret_cast<unsigned*>(w.err), nzero, reinterpret_cast<f32x4*>(w.ring), ns1,
                      reinterpret_cast<f32x4*>(w.zring + nzb), ns2);
   DAMC_LAUNCH_CHECK();
   double flops_step = 0;

@@ -895,49 +895,38 @@ __global__ __launch_bounds__(256, 2) void gemm_km_kernel(GemmArgs p) {
   }
 }
 
-// The first layer's input gradient at per-rank batches (dz_slabs: M = B <= 32 dense rows as a 1 x 1 "convolution",
-// split-K slices of k_per_z, EPI_STORE into per-slice slabs): one workgroup per (slice, 128 columns), 4 waves of 32
+// The first layer's input gradient at per-rank batches (dz_slabs: M = B dense rows as a 1 x 1 "convolution",
+// split-K slices of k_per_z, EPI_STORE into per-slice slabs): one workgroup per (slice, 128 columns, 32 rows), 4 waves of 32
 // columns, every fragment straight from memory into registers with 4 K tiles' loads in flight (the 128 x 128 kernel
 // walks a slice's 8 K tiles through a 2-3 deep LDS pipeline, latency-bound at this size).  The same 32x32x2 MFMA
 // sequence per output (k-quad q, then step s; lane half lk takes k = 8 q + 4 lk + s of each 32-deep tile) from zero
 // per slice, so every slab value is bitwise gemm_km_kernel's.
-// MT = 2 (round 5, DAMC_KM_SKINNY_MT=2 since round 6): M <= 64 as two 32-row tiles per wave (SVHN's per-config batch of 64 at nz = 100 left the tiled
-// kernel 22 us for a 52 MFLOP product), two K tiles' loads in flight so the fragments stay within the VGPRs
-template <int MT>
 __global__ __launch_bounds__(256) void km_skinny_kernel(GemmArgs p) {
-  constexpr int KU = 4 / MT;
+  constexpr int KU = 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lrow = lane & 31, lk = lane >> 5;
-  // blockIdx.z: 32 MT-row block of the rows (round 5: M up to 128 as two 64-row blocks)
-  const int z = blockIdx.x, n0 = blockIdx.y * 128 + wave * 32, rb0 = blockIdx.z * 32 * MT;
+  const int z = blockIdx.x, n0 = blockIdx.y * 128 + wave * 32, rb0 = blockIdx.z * 32;
   const int kbeg = z * p.k_per_z, kend = min(p.K, kbeg + p.k_per_z);
   const int nk = kend > kbeg ? (kend - kbeg) / KM_BK : 0;
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, p.M * p.Cg * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb =
       __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, p.N * (int)p.ldb * 4, 0x00020000);
   constexpr int OOB = 0x7FFFFFF0;
-  int aoff[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-    aoff[t] = rb0 + 32 * t + lrow < p.M ? ((rb0 + 32 * t + lrow) * p.Cg + 4 * lk) * 4 : OOB;
+  const int aoff = rb0 + lrow < p.M ? ((rb0 + lrow) * p.Cg + 4 * lk) * 4 : OOB;
   const int boff = n0 + lrow < p.N ? ((n0 + lrow) * (int)p.ldb + 4 * lk) * 4 : OOB;
-  f32x16 acc[MT];
+  f32x16 acc;
 #pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   for (int kt = 0; kt < nk; kt += KU) {
-    f32x4 fa[MT][KU][4], fb[KU][4];
+    f32x4 fa[KU][4], fb[KU][4];
 #pragma unroll
     for (int u = 0; u < KU; ++u)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const bool live = kt + u < nk;
         const int k0 = (kbeg + (kt + u) * KM_BK + 8 * q) * 4;
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-          fa[t][u][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                      ra, live ? aoff[t] : OOB, live ? k0 : 0, 0));
+        fa[u][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                 ra, live ? aoff : OOB, live ? k0 : 0, 0));
         fb[u][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                                  rb, live ? boff : OOB, live ? k0 : 0, 0));
       }
@@ -949,19 +938,15 @@ __global__ __launch_bounds__(256) void km_skinny_kernel(GemmArgs p) {
       for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-          for (int t = 0; t < MT; ++t)
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[t][u][q][s2], fb[u][q][s2], acc[t], 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[u][q][s2], fb[u][q][s2], acc, 0, 0, 0);
     }
   }
   float* Cz = p.C + (long)z * p.c_zstride;
 #pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = rb0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * lk, n = n0 + lrow;
-      if (m < p.M && n < p.N) Cz[(long)m * p.ldc + n] = acc[t][r];
-    }
+  for (int r = 0; r < 16; ++r) {
+    const int m = rb0 + (r & 3) + 8 * (r >> 2) + 4 * lk, n = n0 + lrow;
+    if (m < p.M && n < p.N) Cz[(long)m * p.ldc + n] = acc[r];
+  }
 }
 
 template <int EPI, int OM, int PIPE = DAMC_KM_PIPE, int DBG = 0>
@@ -1003,22 +988,15 @@ static int launch_gemm_km(const GemmArgs& a, Epi epi, OMode om, int zdim, hipStr
     // dz_slabs at per-rank batches: km_skinny_kernel (bitwise gemm_km_kernel); DAMC_KM_SKINNY=0 (read per call) keeps
     // the tiled kernel
     const char* esk = getenv("DAMC_KM_SKINNY");
-    // rows: up to 64 (two 32-row tiles per wave); DAMC_KM_SKINNY_ROWS (read per call) moves the limit for A/B (128, as
-    // two 64-row blocks: 38.3 us against the tiled kernel's 28.6 at the headline's B = 128, profiles/r05/skinny128_ab.txt)
+    // rows: up to 64, in 32-row workgroups (round 6: SVHN B=64's two workgroups per slice took 11.4 us against 17.2 for
+    // one 64-row workgroup of two tiles per wave, profiles/r06/km_skinny_mt.txt); DAMC_KM_SKINNY_ROWS (read per call)
+    // moves the limit for A/B against the tiled kernel
     const char* ekr = getenv("DAMC_KM_SKINNY_ROWS");
     const int km_rows = ekr ? atoi(ekr) : 64;
     if (epi == EPI_STORE && om == O_DENSE && c.M <= km_rows && c.Hin == 1 && c.Win == 1 && c.Hq == 1 && c.Wq == 1 &&
         c.kw == 1 && c.Cg == c.K && !(esk && esk[0] == '0')) {
-      // rows in 32-row workgroups of km_skinny_kernel<1> (round 6: SVHN B=64's two workgroups per slice took 11.4 us
-      // against 17.2 for one 64-row workgroup of <2>, half the MFMA chain per wave, profiles/r06/km_skinny_mt.txt);
-      // DAMC_KM_SKINNY_MT=2 (read per call) keeps <2> for 33-64 rows
-      const char* emt = getenv("DAMC_KM_SKINNY_MT");
-      const bool mt1 = c.M <= 32 || !(emt && emt[0] == '2');
-      const dim3 g((unsigned)zdim, (unsigned)((c.N + 127) / 128), (unsigned)((c.M + (mt1 ? 31 : 63)) / (mt1 ? 32 : 64)));
-      if (mt1)
-        hipLaunchKernelGGL(km_skinny_kernel<1>, g, dim3(256), 0, s, c);
-      else
-        hipLaunchKernelGGL(km_skinny_kernel<2>, g, dim3(256), 0, s, c);
+      const dim3 g((unsigned)zdim, (unsigned)((c.N + 127) / 128), (unsigned)((c.M + 31) / 32));
+      hipLaunchKernelGGL(km_skinny_kernel, g, dim3(256), 0, s, c);
       continue;
     }
 #define DAMC_KM(E_, O_)                \
@@ -1068,9 +1046,6 @@ constexpr int X3_F32A = 2097152, X3A_ROWB = 128;
 // 74 KB of LDS so two workgroups share a CU: a small-batch conv fills the chip without split-K slabs (every output
 // takes the default tile's MFMA sequence, so it is bitwise the default and the split forms)
 constexpr int X3_NARROW = 4194304;
-// split-K with the in-GEMM ordered fix-up (GemmArgs::kticket; the F32A register-slab path): the last workgroup of a
-// tile to arrive sums the tile's slabs in slab order and runs the unsplit epilogue, so no reduce launch follows
-constexpr int X3_FIXUP = 8388608;
 // X3_TAPSHARE (round 7; F32A with the slice-major walk GemmArgs::kwalk, an Hq x Wq grid that x3_tapshare_ok accepts):
 // the four K tiles of a group (one 32-channel slice x the four taps of a ConvT phase, or of a parity class of the
 // stride-2 4 x 4 conv) read the same 256 input pixels displaced by 0 / +-1 grid positions, so the undisplaced 256 x
@@ -1078,8 +1053,6 @@ constexpr int X3_FIXUP = 8388608;
 // fragment read takes LDS row r + delta(tap), or a 128-B all-zero row where the tap falls in the padding: 8 KB instead
 // of 32 KB of A per K tile, the same fp32 operands, bitwise the per-tap staging
 constexpr int X3_TAPSHARE = 16777216;
-constexpr int X3_FIXUP_WAIT = 3000;  // the fix-up's bounded wait for the other slices: 30 us of s_memrealtime (100 MHz)
-static unsigned* g_fixup_probe = nullptr;  // damc_x3_fixup_probe (diagnostics)
 __device__ __forceinline__ int f32a_swz(int r) { return ((r >> 1) & 7) ^ ((((r >> 2) ^ (r >> 3)) & 1) << 1); }
 // the swizzle of the X3_TAPSHARE image: a tap's fragment read takes rows r + delta, so the 16 rows of a ds_read_b128
 // lane group arrive rotated by any delta mod 16, where f32a_swz is 2-way for every rotation but 0 and 8.  With row bit
@@ -1103,9 +1076,9 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 //                half-empty tile at M = 128 (the first layer, M = B) and half the A gather per K tile
 //   X3_KREG      split-K into register-layout slabs (GemmArgs::kslab_reg; launched only split, 256 x 128 tiles): a
 //                compile-time variant, so the block-total registers of the unsplit kernel drop out
-//   X3_F32A, X3_NARROW, X3_FIXUP, X3_TAPSHARE: above
+//   X3_F32A, X3_NARROW, X3_TAPSHARE: above
 constexpr int X3_BASE = 261, X3_RASTER = 16, X3_WIDE = 524288, X3_KREG = 1048576;
-constexpr int X3_BITS = X3_BASE | X3_RASTER | X3_WIDE | X3_KREG | X3_F32A | X3_NARROW | X3_FIXUP | X3_TAPSHARE;
+constexpr int X3_BITS = X3_BASE | X3_RASTER | X3_WIDE | X3_KREG | X3_F32A | X3_NARROW | X3_TAPSHARE;
 // RNE limb split of 8 consecutive values: v = h + m + l (to 24 significand bits)
 __device__ __forceinline__ void split3_octet(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
 #pragma unroll
@@ -1139,25 +1112,6 @@ __device__ __forceinline__ void proj16(const float* tile, int ts, int r0, int C,
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], acc[t], 0, 0, 0);
     }
-  }
-}
-
-// proj16 with the b operands preloaded into registers (w[g][t] = weight row 16 t + m, k = 16 g + 4 q .. + 3, as
-// x3_ksplit_reduce_proj_kernel holds them): the same MFMA sequence per output, so bitwise proj16
-template <int NT>
-__device__ __forceinline__ void proj16_pre(const float* tile, int ts, int r0, int C, const f32x4 (&w)[PROJ_CHUNK / 16][4],
-                                           f32x4 (&acc)[NT]) {
-  const int lane = threadIdx.x & 63, m = lane & 15, q = lane >> 4;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int g = 0; g < PROJ_CHUNK / 16; ++g) {
-    if (16 * g >= C) break;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(tile + (r0 + m) * ts + 16 * g + 4 * q);
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], w[g][t][e], acc[t], 0, 0, 0);
   }
 }
 
@@ -1260,9 +1214,6 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   const bool KSPLIT = OM != O_WGRAD && p.ksplit > 1;
   constexpr bool KREG = (V & X3_KREG) != 0;  // register-layout slabs (launched only split)
   static_assert(!KREG || !WIDE, "KREG: 256 x 128 tiles only");
-  // in-GEMM ordered fix-up of the split-K slabs (round 6; the protocol is described where the epilogue runs it)
-  constexpr bool FIXUP = (V & X3_FIXUP) != 0;
-  static_assert(!FIXUP || (KREG && F32A), "FIXUP: the F32A register-slab split-K path");
   constexpr bool TSHARE = (V & X3_TAPSHARE) != 0;
   static_assert(!TSHARE || F32A, "TAPSHARE: the F32A path (on the slice-major walk)");
   const int nslz = KSPLIT ? p.ksplit / p.kbpw : 1;
@@ -1761,8 +1712,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
               // With soffset = 0 the recognizer pads the hazard itself (profiles/r06/kreg_store_isa.txt);
               // test_f32a_posterior_is_bitwise (B=16, register slabs) stays the gate
               __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc16[i][j]), rsl,
-                                                     voff + soff + (wnp * 1024 + (a * 4 + j) * 64) * 16, 0,
-                                                     FIXUP ? 16 : 0);
+                                                     voff + soff + (wnp * 1024 + (a * 4 + j) * 64) * 16, 0, 0);
             }
             acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
           }
@@ -1884,8 +1834,8 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     c[2] = t1;
     c[3] = r1;
   }
-  if (KREG && !FIXUP) return;  // every block already in its slab
-  if constexpr (!FIXUP) {  // the last partial block
+  if (KREG) return;  // every block already in its slab
+  {  // the last partial block
     const float sg = (p.b_negblk && nk > 0 && (((nk - 1 + kt0) >> FLOG) & 1)) ? -1.f : 1.f;
     constexpr int MI = NARROW ? 2 : 4;
 #pragma unroll
@@ -1899,7 +1849,6 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   // 2 x 16-B fp32 stores and (C3) 3 x 16-B limb stores per octet, each row's 128 channels contiguous
   constexpr int TS = BN + 4;  // tile row stride (floats): 4-row groups of a 16x16 store land 16 banks apart
   static_assert(BM * TS * 4 + BM * 8 <= 2 * (BM + BN) * X3_ROWB, "epilogue tile exceeds the LDS");
-  static_assert(!FIXUP || BM * TS * 4 + BM * 8 <= 2 * (BM + BN) * X3_ROWB - 16, "the fix-up's last word overlaps the tile");
   float* tile = reinterpret_cast<float*>(smem);
   long* rowtab = reinterpret_cast<long*>(smem + BM * TS * 4);
   float* Cz = p.C;
@@ -1961,19 +1910,11 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
       *reinterpret_cast<f32x4*>(tile + row * TS + oct * 8 + 4) = f32x4{v[4], v[5], v[6], v[7]};
     }
   };
-  // FIXUP: the output-layer projection's weights (proj16's b operands of this N tile's chunk), preloaded into registers
-  // while the slices wait, so a band's projection does not chain on their loads (proj16_pre)
-  f32x4 pw[PROJ_CHUNK / 16][4];
-  // the epilogue of tile rows [r_lo, r_hi) (the whole tile except in the fix-up's bands; rowtab is -1 outside)
-  auto epilogue = [&](int r_lo, int r_hi) {
-    if constexpr (FIXUP) {
-      for (int id = tid; id < (r_hi - r_lo) * (BN / 8); id += 512) octet(r_lo + id / (BN / 8), id % (BN / 8));
-    } else {
+  auto epilogue = [&]() {  // the whole tile
 #pragma unroll 2
-      for (int it = 0; it < BM * BN / 8 / 512; ++it) {
-        const int id = tid + 512 * it;
-        octet(id / (BN / 8), id % (BN / 8));
-      }
+    for (int it = 0; it < BM * BN / 8 / 512; ++it) {
+      const int id = tid + 512 * it;
+      octet(id / (BN / 8), id % (BN / 8));
     }
     if constexpr (OM == O_PHASE && EPI == EPI_BIAS_ACT && (WIDE || F32A)) {
       // fused output-layer projection (GemmArgs::proj_out), proj16 as proj_rows_kernel, P indexed by the output pixel,
@@ -1989,15 +1930,14 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
 #pragma unroll
           for (int g = 0; g < RG; ++g) {
             const int r0 = F32A ? wave * 32 + g * 16 : wave * 16;
-            if (r0 + 16 <= r_lo || r0 >= r_hi) continue;  // FIXUP: a 16-row group outside the band (wave-uniform)
+            // one row group at a time: scheduled across this point, the F32A ConvT forward (CIFAR B=128) measured
+            // 0.8 % slower
+            __builtin_amdgcn_sched_barrier(0);
             for (int c0 = 0; c0 < (F32A ? BN : p.N); c0 += PROJ_CHUNK) {
               const int cc = F32A ? n0 : c0;  // global channel of the chunk's first column
               if (cc >= p.N) break;
               f32x4 acc[NT];
-              if constexpr (FIXUP)
-                proj16_pre<NT>(tile + c0, TS, r0, min(PROJ_CHUNK, p.N - cc), pw, acc);
-              else
-                proj16<NT>(tile + c0, TS, r0, min(PROJ_CHUNK, p.N - cc), p.proj_w + cc, p.proj_ldw, acc);
+              proj16<NT>(tile + c0, TS, r0, min(PROJ_CHUNK, p.N - cc), p.proj_w + cc, p.proj_ldw, acc);
               float* Pc = p.proj_out + (cc / PROJ_CHUNK) * p.proj_pstride;
 #pragma unroll
               for (int t = 0; t < NT; ++t)
@@ -2016,163 +1956,6 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
       }
     }
   };
-  if constexpr (FIXUP) {
-    // ---- split-K in-GEMM ordered fix-up, spread over the tile's slices (MI355X_MICROARCH.md, inter-workgroup visibility,
-    // first row of the sc1 hand-off table).  Every slice stored its slabs sc1 (write-through); each wave drains them,
-    // then behind a barrier lane 0 counts the slice in (one agent-scope CAS on the tile's epoch-tagged counter) and waits,
-    // bounded, until every slice of the tile has arrived (the launch has <= 256 workgroups at one per CU, so they are
-    // co-resident on an otherwise idle chip).  Slice j then claims band j of the tile's 16-row tiles (a CAS on the band's
-    // claim word, exactly once per launch) and sums the band's slabs 0 .. ksplit - 1 in order with sc1 loads into the LDS
-    // tile -- x3_ksplit_reduce_tile_kernel's order and roundings -- and runs the unsplit epilogue on those rows.  The last
-    // slice to arrive never waits: after its own band it claims every band still unclaimed (a slice whose wait ran out
-    // leaves its band), so each band is combined exactly once whatever the residency.  Words are tagged with the launch's
-    // epoch (GemmArgs::kepoch), so the counters need zeroing once per call, not per launch.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const unsigned long long t_drained = __builtin_amdgcn_s_memrealtime();
-    // LDS words past the epilogue's tile and row table, in the one LDS array: [0] own band claimed, [1] last, [2] bands
-    unsigned* sw = reinterpret_cast<unsigned*>(smem + sizeof(smem) - 16);
-    const int ntile = ((p.M + BM - 1) / BM) * ntn;
-    const int tix = zph * ntile + tm * ntn + tn;
-    const int nband = min(nslz, 16);
-    const unsigned ep = p.kepoch;
-    unsigned* cnt = p.kticket + tix;
-    unsigned* claim = p.kticket + X3_KTICKETS + (long)tix * nslz;
-    auto try_claim = [&](int b) -> bool {
-      unsigned w = __hip_atomic_load(claim + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      while ((w >> 16) != ep)
-        if (__hip_atomic_compare_exchange_strong(claim + b, &w, (ep << 16) | 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-          return true;
-      return false;
-    };
-    if constexpr (OM == O_PHASE && EPI == EPI_BIAS_ACT) {
-      if (p.proj_out) {  // F32A: this N tile is the chunk n0 / PROJ_CHUNK
-        const int cw = min(PROJ_CHUNK, p.N - n0), nt = p.proj_np / 16, mm = lane & 15, qq = lane >> 4;
-        // buffer loads, zeros past the chunk's columns or rows through an out-of-range offset (no branch per load)
-        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)p.proj_w, (short)0, p.proj_np * p.proj_ldw * 4, 0x00020000);
-#pragma unroll
-        for (int g = 0; g < PROJ_CHUNK / 16; ++g)
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-            pw[g][t] = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                           rw, (16 * g < cw && t < nt) ? (n0 + (16 * t + mm) * p.proj_ldw + 16 * g + 4 * qq) * 4
-                                                       : (int)KM_OOB, 0, 0));
-      }
-    }
-    if (tid == 0) {
-      unsigned w = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), mine;
-      for (;;) {
-        mine = ((w >> 16) == ep ? (w & 0xFFFFu) : 0u) + 1u;
-        if (__hip_atomic_compare_exchange_strong(cnt, &w, (ep << 16) | mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-          break;
-      }
-      const bool last = mine == (unsigned)nslz;
-      bool ok = last;
-      if (!last) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        unsigned long long dt = 0;
-        for (;;) {
-          const unsigned v = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          dt = __builtin_amdgcn_s_memrealtime() - t0;
-          if ((v >> 16) == ep && (v & 0xFFFFu) >= (unsigned)nslz) {
-            ok = true;
-            break;
-          }
-          if (dt > (unsigned long long)X3_FIXUP_WAIT) break;
-          __builtin_amdgcn_s_sleep(2);
-        }
-        if (p.fixup_probe) {
-          atomicMax(p.fixup_probe + 3, (unsigned)dt);
-          atomicAdd(p.fixup_probe + 4, (unsigned)dt);
-        }
-      }
-      sw[0] = (ok && zsl < nband && try_claim(zsl)) ? 1u : 0u;
-      sw[1] = last ? 1u : 0u;
-      if (p.fixup_probe) {
-        atomicAdd(p.fixup_probe, 1u);
-        if (!ok) atomicAdd(p.fixup_probe + 1, 1u);
-        if (last) atomicAdd(p.fixup_probe + 5, 1u);
-      }
-    }
-    __syncthreads();
-    // damc_clock_probe on a fix-up launch (diagnostics): realtime stamps {K-loop end, slabs drained, wait over, bands
-    // done} instead of the clock pairs
-    unsigned long long* ck = (p.clk && tid == 0)
-                                 ? p.clk + 4 * ((blockIdx.z * gridDim.x + blockIdx.x) % (unsigned)p.clk_n) : nullptr;
-    if (ck) {
-      ck[0] = ck[3];  // K-loop end
-      ck[1] = t_drained;
-      ck[2] = __builtin_amdgcn_s_memrealtime();  // wait over
-    }
-    const bool own_ok = sw[0] != 0, last = sw[1] != 0;
-    const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.kslab + (long)zph * p.ksplit * ntile * (BM * BN)), (short)0, p.ksplit * ntile * (BM * BN) * 4,
-        0x00020000);
-    // band b = 16-row tiles [16 b / nband, 16 (b + 1) / nband): thread (wn = tid >> 8, column tile ci, lane l) owns one
-    // f32x4 of the register slab layout per row tile (rows 4 (l >> 4) .. + 3, column wn 64 + ci 16 + (l & 15)); the
-    // (row tile, slab) pairs go 16 loads at a time, each added into the LDS tile in slab order (0 + slab 0 + slab 1 ..)
-    auto band = [&](int b) {
-      const int rt0 = b * 16 / nband, rt1 = (b + 1) * 16 / nband, np = (rt1 - rt0) * p.ksplit;
-      const int wnb = tid >> 8, ci = (tid >> 6) & 3;
-      __syncthreads();  // the previous band's epilogue is done with the tile
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};  // the running sum of the current row tile's slabs
-      for (int q0 = 0; q0 < np; q0 += 16) {
-        f32x4 t[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-          const int q = q0 + k, rt = rt0 + q / p.ksplit, sl = q - (q / p.ksplit) * p.ksplit;
-          const int off = ((((rt >> 2) * 2 + wnb) * 16 + (rt & 3) * 4 + ci) * 64 + lane) * 16;
-          // no branch around the load (a "load or zero" select made each load wait for the last one): an invalid
-          // pair's offset falls outside the buffer, which returns zeros
-          t[k] = __builtin_bit_cast(
-              f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsl, (q < np && m0 + rt * 16 < p.M) ? off : (int)KM_OOB,
-                                                           (sl * ntile + tm * ntn + tn) * (BM * BN * 4), 16));
-        }
-        __builtin_amdgcn_sched_barrier(0);  // all 16 loads issued before the first add waits on one
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-          const int q = q0 + k, rt = rt0 + q / p.ksplit, sl = q - (q / p.ksplit) * p.ksplit;
-          // 0 + slab 0 + slab 1 + ..., as the reduce; pairs past the band leave acc alone (a select, no branch)
-          const f32x4 nx = (sl == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc) + t[k];
-          acc = q < np ? nx : acc;
-          if (q < np && sl == p.ksplit - 1) {
-            float* d = tile + (rt * 16 + 4 * (lane >> 4)) * TS + wnb * 64 + ci * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) d[r * TS] = acc[r];
-          }
-        }
-      }
-      if (tid < BM)
-        rowtab[tid] = (tid >= rt0 * 16 && tid < rt1 * 16 && m0 + tid < p.M) ? gemm_row_offset<OM>(p, m0 + tid, py, px)
-                                                                           : -1L;
-      __syncthreads();
-      epilogue(rt0 * 16, rt1 * 16);
-    };
-    if (own_ok) band(zsl);
-    if (last) {
-      if (wave == 0) {  // the bands nobody claimed, one CAS per band in parallel lanes
-        const bool got = lane < nband && lane != zsl && try_claim(lane);
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(got);
-        if (lane == 0) {
-          sw[2] = (unsigned)m;
-          if (p.fixup_probe && m) atomicAdd(p.fixup_probe + 2, (unsigned)__builtin_popcountll(m));
-        }
-      }
-      __syncthreads();
-      unsigned m = sw[2];
-      while (m) {
-        const int b = __builtin_ctz(m);
-        m &= m - 1;
-        band(b);
-      }
-    }
-    if (ck) ck[3] = __builtin_amdgcn_s_memrealtime();
-    return;
-  }
   if (tid < BM) rowtab[tid] = (m0 + tid < p.M) ? gemm_row_offset<OM>(p, m0 + tid, py, px) : -1L;
   if (F32A) {
 #pragma unroll
@@ -2201,7 +1984,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
           tile[(wm * 64 + i * 16 + 4 * (lane >> 4) + r) * TS + wn * 64 + j * 16 + (lane & 15)] = acc16[i][j][r];
   }
   __syncthreads();
-  if (KSPLIT && !FIXUP) {  // row-major slabs (one block per workgroup): the fp32 tile into its slab; the reduce applies the epilogue
+  if (KSPLIT) {  // row-major slabs (one block per workgroup): the fp32 tile into its slab; the reduce applies the epilogue
     float* sl = p.kslab + ((long)zph * p.ksplit + zsl) * p.M * p.N;
 #pragma unroll 2
     for (int it = 0; it < BM * BN / 8 / 512; ++it) {
@@ -2214,8 +1997,8 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     }
     return;
   }
-  epilogue(0, BM);
-  if constexpr (OM == O_DENSE && EPI == EPI_BIAS_ACT && !WIDE && !NARROW && !FIXUP && BM == 256 && BN == 128) {
+  epilogue();
+  if constexpr (OM == O_DENSE && EPI == EPI_BIAS_ACT && !WIDE && !NARROW && BM == 256 && BN == 128) {
     // the encoder norm's statistics of this tile (GemmArgs::in_part): its 256 rows are one strip of one sample
     static_assert(BM * TS * 4 + BM * 8 + 1024 * 4 <= 2 * (BM + BN) * X3_ROWB, "statistics scratch exceeds the LDS");
     if (p.in_part && !KSPLIT) {  // workgroup-uniform
@@ -2628,8 +2411,8 @@ static bool x3_tapshare_on() {
   return !(e && e[0] == '0');
 }
 
-// V: X3_BASE, + X3_F32A, or + X3_WIDE, as launch_gemm_x3 chooses; X3_TAPSHARE, X3_NARROW, X3_KREG, X3_FIXUP and
-// X3_RASTER are added here
+// V: X3_BASE, + X3_F32A, or + X3_WIDE, as launch_gemm_x3 chooses; X3_TAPSHARE, X3_KREG and X3_RASTER are added here
+// (X3_NARROW: launch_x3_narrow_split)
 template <int EPI, int OM, int V = X3_BASE>
 static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
   static_assert(OM != O_WGRAD && (V & X3_BASE) == X3_BASE && !(V & ~(X3_BASE | X3_F32A | X3_WIDE | X3_TAPSHARE)) &&
@@ -2655,24 +2438,6 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
   if (a.in_part && !(OM == O_DENSE && EPI == EPI_BIAS_ACT && !WIDE && zdim == 1 && a.in_hw > 0 &&
                      a.in_hw % 256 == 0 && a.M % a.in_hw == 0 && a.in_S == a.in_hw / 256))
     no_stats();
-  if constexpr (V == X3_BASE) {
-    // opt-in (DAMC_X3_NARROW=1, read per call): an under-filled grid that the 64 x 128 tile fills (>= 256 workgroups)
-    // runs unsplit on it instead of split-K.  Measured slower at the CIFAR B=16 per-rank step: 158.7 / 152.2 us for the
-    // L2 forward / L3 dgrad against 121 / 122 us for split-K + reduce (profiles/r04/b16_narrow_kernel_stats.csv): the
-    // 32 x 32 wave tile reads 2x the LDS fragments per MFMA and stages 1.5x the bytes per flop
-    const char* en = getenv("DAMC_X3_NARROW");
-    const long nnm = (a.M + 63) / 64;
-    if (a.kslab && !a.proj_out && en && en[0] == '1' && (long)ntm * ntn * zdim < 256 &&
-        nnm * ntn * zdim >= 256) {
-      no_stats();
-      a.ksplit = 1;
-      a.kbpw = 1;
-      a.kslab_reg = 0;
-      hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, X3_BASE | X3_NARROW>), dim3((unsigned)(nnm * ntn), 1, zdim), dim3(512),
-                         0, s, a);
-      return 0;
-    }
-  }
   if (a.kslab) {
     const int ks = x3_ksplit(a.M, a.N, a.K, zdim, BM, BN, a.negk);
     if (ks > 1 && (long)zdim * ks * a.M * a.N <= a.kslab_floats && a.N % 8 == 0) {
@@ -2708,25 +2473,6 @@ static int launch_x3_t(const GemmArgs& a0, int zdim, hipStream_t s) {
       a.kbpw = bpw;
       a.k_per_z = a.K / ks * bpw;
       if constexpr (!WIDE) {
-        if constexpr (F32A && ((EPI == EPI_BIAS_ACT && OM == O_PHASE) || (EPI == EPI_MASK && OM == O_DENSE))) {
-          // round 6, opt-in (DAMC_X3_FIXUP=1, read per call): the in-GEMM ordered fix-up instead of the reduce launch
-          // (bitwise; gemm_x3_kernel X3_FIXUP) where the caller provides zeroed counters.  Measured slower at every
-          // per-rank batch (CIFAR B=16 0.474-0.485 against 0.410 ms per step, SVHN B=64 0.386-0.391 against
-          // 0.216-0.226; profiles/r06/fixup_ab.txt): the slabs' write-through, the wait for the tile's slowest slice
-          // and the bands' reads of 32 MB of slabs put 15-20 us on every launch's tail (profiles/r06/fixup_timeline.txt),
-          // more than the 9-17 us reduce launch they replace
-          const char* ef = getenv("DAMC_X3_FIXUP");
-          const long grid = (long)ntm * ntn * zdim * (ks / bpw);
-          if (a.kslab_reg && a.kticket && a.kepoch_ctr && *a.kepoch_ctr < 65535u && ef && ef[0] == '1' &&
-              grid <= 256 && grid <= X3_KTICKETS && (long)ks * ntm * ntn * BM * BN * 4 < (1L << 31)) {
-            a.kepoch = ++*a.kepoch_ctr;  // this launch's tag on the counters and claims (16 bits; zeroed per call)
-            a.fixup_probe = g_fixup_probe;
-            a.proj_nostore = nostore0;  // the epilogue runs the fused projection itself, as the unsplit kernel does
-            hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V | X3_KREG | X3_FIXUP>), dim3(ntm * ntn, 1, zdim * ks / bpw),
-                               dim3(512), 0, s, a);
-            return 0;
-          }
-        }
         if (a.kslab_reg)
           hipLaunchKernelGGL((gemm_x3_kernel<EPI, OM, V | X3_KREG>), dim3(ntm * ntn, 1, zdim * ks / bpw), dim3(512), 0,
                              s, a);
@@ -3427,8 +3173,6 @@ int launch_gemm(const GemmArgs& a, AMode am, Epi epi, OMode om, int zdim, const 
   return DAMC_ERR_UNSUPPORTED;
 }
 
-void set_fixup_probe(unsigned* buf) { g_fixup_probe = buf; }
-
 void set_clock_probe(unsigned long long* buf, int n) {
   g_clk = (buf && n > 0) ? buf : nullptr;
   g_clk_n = g_clk ? n : 0;
@@ -3445,11 +3189,6 @@ extern "C" int damc_clock_probe(unsigned long long* buf, int n_slots) {
 
 extern "C" unsigned long long damc_x3_tapshare_launches(void) {
   return damc::g_tapshare_launches.load(std::memory_order_relaxed);
-}
-
-extern "C" int damc_x3_fixup_probe(unsigned* buf) {
-  damc::set_fixup_probe(buf);
-  return 0;
 }
 
 extern "C" int damc_gemm(const float* a, int lda, const float* b, int ldb, const float* bias, float* c, int ldc,

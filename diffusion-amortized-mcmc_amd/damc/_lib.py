@@ -200,12 +200,10 @@ _SIGS = {
     "damc_conv2d_x3_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "damc_conv2d_x3_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "damc_clock_probe": (_I, [_P, _I]),
-    "damc_x3_fixup_probe": (_I, [_P]),
     "damc_x3_conv_walk": (_I, [_I, _I]),
     "damc_pack_conv2d_x3": (_I, [_P, _I, _I, _I, _P, _P]),
     "damc_sweep_workspace_bytes": (_SZ, [ctypes.POINTER(Denoiser), _I, _I]),
     "damc_sweep_team_failures": (ctypes.c_long, [_I]),
-    "damc_sweep_team_words": (_I, [ctypes.POINTER(Denoiser), _I, _I, _P, _SZ, _P, _I]),
     "damc_reverse_sweep": (_I, [ctypes.POINTER(Denoiser), _P, _P, _I, _I, _P, _P, _I, _P, _U64, _U64, _P, _I, _P,
                                 _SZ, _P]),
     "damc_q_reverse_sweep": (_I, [ctypes.POINTER(Denoiser), _P, _P, _I, _I, _P, _P, _I, _P, _U64, _U64, _P, _I, _P,

@@ -282,10 +282,6 @@ unsigned long long damc_x3_tapshare_launches(void);
  * clock the chip holds in that loop is d(memtime) / d(realtime) x 100 MHz.  buf = NULL switches it off.  Not
  * thread-safe; keep it off in timed work (bench.py runs it on one extra block). */
 int damc_clock_probe(unsigned long long* buf, int n_slots);
-/* diagnostics: while buf (8 uint32, device memory, zeroed by the caller) is set, every split-K launch with the in-GEMM
- * fix-up (gemm.hip X3_FIXUP) adds to it: [0] workgroups, [1] waits that ran out, [2] bands the last arrivers took over,
- * [3] the longest wait (s_memrealtime ticks, 100 MHz), [4] the waits' total ticks, [5] last arrivers.  NULL: off */
-int damc_x3_fixup_probe(unsigned* buf);
 /* a Conv2d weight in its PyTorch layout (cout, cin, k, k), cin % 32 == 0 -> the limb engine's B operand of the
  * conv (damc_conv2d_x3_bytes bytes), in one pass */
 int damc_pack_conv2d_x3(const float* w, int cout, int cin, int k, void* w_x3, void* stream);
@@ -374,12 +370,8 @@ int damc_q_reverse_sweep(const damc_denoiser_t* d, const float* xemb, float* zt,
  * process or stream holding CUs), its bounded waits give up and the library recomputes the affected sweep on the
  * device (bitwise the team's arithmetic; never NaN), flags the device, and runs later sweeps on the launch chain.
  * damc_sweep_team_failures: how many such rescued launches this process has seen on a device (a rescue still in
- * flight is counted once it completes).  damc_sweep_team_words (tools; synchronises the device): the workspace's
- * team control words (flags [8][64][32], error word, then per workgroup {stage needed, first late flag, late-slot
- * mask lo, hi} of a failed wait). */
+ * flight is counted once it completes). */
 long damc_sweep_team_failures(int device);
-int damc_sweep_team_words(const damc_denoiser_t* d, int batch, int n_steps, const void* workspace,
-                          size_t workspace_bytes, int* out, int nwords);
 /* per-op hook (SURVEY.md §8b damc_denoise_step): ONE reverse step = damc_reverse_sweep with n_steps = 1 on the
  * step's temb_row (ntemb) and coef_row (6, HOST); noise (B, nz) injected or NULL for Philox at step index
  * noise_step (the k-th noisy step of a sweep uses k); eps (B, nz) receives the denoiser output or NULL.

@@ -340,11 +340,9 @@ def test_split_k_is_bitwise_the_unsplit_kernel(lv, gpu_device, monkeypatch, net,
     """Split-K of the limb-engine convs at small batch (gemm.hip x3_ksplit: one sign block per slice, summed in the
     kernel's order and rounding) gives the same bits as the unsplit kernel: 3 posterior steps at full width with
     DAMC_X3_KSPLIT=0 vs the default -- F32A, register slabs, the reduce launch with the fused output-layer projection
-    -- vs the two-kernel projection (DAMC_REDUCE_PROJ=0) and the round-6 in-GEMM ordered fix-up (DAMC_X3_FIXUP=1,
-    opt-in: every slice of a tile combines one band of its rows once all slices have arrived, the last arriver takes
-    any unclaimed band); and, at CIFAR, the opt-in 64 x 128 tile on the limb-gathering path (gemm.hip X3_NARROW,
-    DAMC_X3_NARROW=1 with DAMC_X3_F32A=0) against all of them.  Per-rank batches of the BASELINE configs: CIFAR B=16
-    (8-way headline), SVHN B=64, CelebA-64 B=32, CelebA-HQ B=8."""
+    -- vs the two-kernel projection (DAMC_REDUCE_PROJ=0); and, at CIFAR, split-K on the limb-gathering path
+    (DAMC_X3_F32A=0) against all of them.  Per-rank batches of the BASELINE configs: CIFAR B=16 (8-way headline),
+    SVHN B=64, CelebA-64 B=32, CelebA-HQ B=8."""
     from damc import synth
     from src import diffusion_net as dn
 
@@ -356,18 +354,15 @@ def test_split_k_is_bitwise_the_unsplit_kernel(lv, gpu_device, monkeypatch, net,
     x = torch.from_numpy(synth.uniform_f32(1, 0, (B, 3, hw, hw))).to(gpu_device)
     z0 = torch.from_numpy(synth.normal_f32(2, 0, (B, nz))).to(gpu_device)
     out = {}
-    modes = [("unsplit", "0", "0", "0", "1"), ("split", "1", "0", "0", "1"), ("fixup", "1", "0", "1", "1"),
-             ("reduce2", "1", "0", "0", "0")]
+    modes = [("unsplit", "0", "1", "1"), ("split", "1", "1", "1"), ("reduce2", "1", "1", "0")]
     if net == "cifar10":
-        modes.append(("narrow", "1", "1", "1", "1"))
-    for mode, split, narrow, fixup, rproj in modes:
+        modes += [("unsplit_limbs", "0", "0", "1"), ("split_limbs", "1", "0", "1")]
+    for mode, split, f32a, rproj in modes:
         # reduce2: the reduce and the output-layer projection as two kernels (DAMC_REDUCE_PROJ=0) instead of the fused
-        # x3_ksplit_reduce_proj_kernel
-        monkeypatch.setenv("DAMC_X3_FIXUP", fixup)
+        # x3_ksplit_reduce_proj_kernel; *_limbs: the limb-gathering path (DAMC_X3_F32A=0)
         monkeypatch.setenv("DAMC_REDUCE_PROJ", rproj)
         monkeypatch.setenv("DAMC_X3_KSPLIT", split)
-        monkeypatch.setenv("DAMC_X3_NARROW", narrow)
-        monkeypatch.setenv("DAMC_X3_F32A", "0" if narrow == "1" else "1")  # the 64 x 128 tile gathers limbs
+        monkeypatch.setenv("DAMC_X3_F32A", f32a)
         z = z0.clone()
         lv.posterior_langevin(z, x, G, E, 3, sigma, 0.1, True, seed=77)
         torch.cuda.synchronize()
@@ -470,25 +465,23 @@ def test_fused_output_projection_is_bitwise(lv, gpu_device, monkeypatch, B, f32a
 @pytest.mark.parametrize("B", [8, 16, 32, 48, 64, 128])
 def test_skinny_first_layer_is_bitwise(lv, gpu_device, monkeypatch, B):
     """The first layer at per-rank batches (B <= 32): z . W on gemm.hip's x3_skinny_kernel and its input gradient's
-    split-K slabs on km_skinny_kernel (fragments straight into registers; up to B = 64 as 32-row workgroups, round
-    6, or as two 32-row tiles per wave, DAMC_KM_SKINNY_MT=2, round 5): 2 noisy posterior steps bitwise equal to
-    the tiled kernels (DAMC_X3_SKINNY=0, DAMC_KM_SKINNY=0), with the skinny kernel reading the weights as fp32 rows
-    split in registers (round 5, default) and as the packed limbs (DAMC_X3_SKINNY_F32B=0)."""
+    split-K slabs on km_skinny_kernel (fragments straight into registers; up to B = 64, as 32-row workgroups): 2 noisy
+    posterior steps bitwise equal to the tiled kernels (DAMC_X3_SKINNY=0, DAMC_KM_SKINNY=0), with the skinny kernel
+    reading the weights as fp32 rows split in registers (round 5, default) and as the packed limbs
+    (DAMC_X3_SKINNY_F32B=0)."""
     G, E, x, z0 = _cifar_full(gpu_device, B)
     out = {}
-    for mode, f32b, mt in (("0", "1", "1"), ("1", "1", "1"), ("1", "0", "1"), ("1", "1", "2")):
+    for mode, f32b in (("0", "1"), ("1", "1"), ("1", "0")):
         monkeypatch.setenv("DAMC_X3_SKINNY", mode)
         monkeypatch.setenv("DAMC_KM_SKINNY", mode)
         monkeypatch.setenv("DAMC_X3_SKINNY_F32B", f32b)
-        monkeypatch.setenv("DAMC_KM_SKINNY_MT", mt)
         z = z0.clone()
         lv.posterior_langevin(z, x, G, E, 2, 0.1, 0.1, True, seed=13)
         torch.cuda.synchronize()
-        out[mode + f32b + mt] = z.cpu()
-    assert torch.isfinite(out["111"]).all()
-    assert torch.equal(out["011"], out["111"])
-    assert torch.equal(out["011"], out["101"])
-    assert torch.equal(out["011"], out["112"])
+        out[mode + f32b] = z.cpu()
+    assert torch.isfinite(out["11"]).all()
+    assert torch.equal(out["01"], out["11"])
+    assert torch.equal(out["01"], out["10"])
 
 
 @pytest.mark.parametrize("net,B", [("cifar10", 100), ("cifar10", 128), ("celeba64", 32)])

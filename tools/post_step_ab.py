@@ -1,6 +1,6 @@
 """Posterior step time (full-width generator + _netE, noise on) over one env switch, interleaved:
 usage: python tools/post_step_ab.py VAR v1,v2 [CASE ...]   CASE = B (CIFAR-10) or net:B, net in cifar10 / svhn /
-celeba64 / celebaHQ; e.g. DAMC_X3_FIXUP 1,0 16 svhn:64 celebaHQ:8"""
+celeba64 / celebaHQ; e.g. DAMC_REDUCE_PROJ 1,0 16 svhn:64 celebaHQ:8"""
 import os
 import sys
 

@@ -12,7 +12,7 @@ from damc import _lib, amortizer, synth  # noqa: E402
 from src import diffusion_net as dn  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
-variants = sys.argv[2:] or ["DAMC_SWEEP_SENT=0", "DAMC_SWEEP_SENT=1"]
+variants = sys.argv[2:] or ["DAMC_SWEEP_LAYOUT=1", "DAMC_SWEEP_LAYOUT=0"]
 dev = torch.device("cuda:0")
 Q = dn._netQ_U(nc=3, nz=128, nxemb=1024, ntemb=128, nif=64, diffusion_residual=True, n_interval=100, logsnr_min=-5.1,
                logsnr_max=9.8, var_type="large", with_noise=True, dataset="cifar10")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Per-stage timing of the one-launch reverse sweep from a DAMC_SWEEP_TRACE dump (100 MHz stamps per workgroup
-and stage: wait begin, wait end, reduced, published).  Workgroup b belongs to team b % 8 (sweep_team_kernel); every
+and stage: task start, wake, reduced, published, as tools/sweep_timeline.py names them).  Workgroup b belongs to team b % 8 (sweep_team_kernel); every
 quantity is taken within a team, relative to that team's last publish of the previous stage, then the median
 over teams and steps is printed per block."""
 import sys
