@@ -1049,15 +1049,17 @@ constexpr int X3_NARROW = 4194304;
 // X3_TAPSHARE (round 7; F32A with the slice-major walk GemmArgs::kwalk, an Hq x Wq grid that x3_tapshare_ok accepts):
 // the four K tiles of a group (one 32-channel slice x the four taps of a ConvT phase, or of a parity class of the
 // stride-2 4 x 4 conv) read the same 256 input pixels displaced by 0 / +-1 grid positions, so the undisplaced 256 x
-// 128-B fp32 image is staged once per group (one 64-row DMA piece per K tile, two image buffers) and each tap's
-// fragment read takes LDS row r + delta(tap), or a 128-B all-zero row where the tap falls in the padding: 8 KB instead
-// of 32 KB of A per K tile, the same fp32 operands, bitwise the per-tap staging
+// 128-B fp32 image is staged once per group (8 KB instead of 32 KB of A per K tile) and, since round 9, split into its
+// limbs once, into an LDS limb image; each tap's fragment reads take limb-image row r + delta(tap), or an all-zero row
+// where the tap falls in the padding: the same limbs of the same fp32 operands, bitwise the per-tap staging.  (Rounds
+// 7-8 under this value: the taps read the fp32 image and each ran the split in registers.)
 constexpr int X3_TAPSHARE = 16777216;
 __device__ __forceinline__ int f32a_swz(int r) { return ((r >> 1) & 7) ^ ((((r >> 2) ^ (r >> 3)) & 1) << 1); }
-// the swizzle of the X3_TAPSHARE image: a tap's fragment read takes rows r + delta, so the 16 rows of a ds_read_b128
-// lane group arrive rotated by any delta mod 16, where f32a_swz is 2-way for every rotation but 0 and 8.  With row bit
-// 1 -> chunk bit 0 and row bit 2 -> chunk bit 2 (the bank group of a 16-B chunk is 8 (row & 1) + chunk) every rotation
-// of every lane group hits 16 distinct bank groups
+// the swizzle of the X3_TAPSHARE fp32 staging image.  Chosen in round 7, when the taps read it at rows r + delta: the
+// 16 rows of a ds_read_b128 lane group then arrive rotated by any delta mod 16, where f32a_swz is 2-way for every
+// rotation but 0 and 8.  With row bit 1 -> chunk bit 0 and row bit 2 -> chunk bit 2 (the bank group of a 16-B chunk is
+// 8 (row & 1) + chunk) every rotation of every lane group hits 16 distinct bank groups; the conversion reads it
+// undisplaced
 __device__ __forceinline__ int ts_swz(int r) { return ((r >> 1) & 1) | (((r >> 2) & 1) << 2); }
 static_assert(X3_NEGK % 32 == 0 && (X3_NEGK & (X3_NEGK - 1)) == 0, "sign blocks are whole K tiles, a power of two");
 constexpr int X3_CHUNKS = 12;  // 16-B chunks per row and K tile (4 octets x 3 limbs)
@@ -1176,11 +1178,19 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   static_assert(!F32A || (OM != O_WGRAD && !WIDE), "F32A: 256 x 128 tiles, not the weight gradient");
   constexpr int AROWB = F32A ? X3A_ROWB : X3_ROWB, ESZ = F32A ? 4 : 6;
   constexpr int AJ = (BM * (F32A ? 8 : X3_CHUNKS) + 511) / 512, BJ = BN * X3_CHUNKS / 512;  // NARROW: 1.5 -> 2
-  // one LDS buffer (A image, then B image; X3_TAPSHARE: then two all-zero 128-B rows)
-  constexpr int BUFB = BM * AROWB + BN * X3_ROWB + ((V & X3_TAPSHARE) ? 2 * X3A_ROWB : 0);
+  // one LDS buffer (A image, then B image)
+  constexpr int BUFB = BM * AROWB + BN * X3_ROWB;
+  // X3_TAPSHARE's LDS instead: the limb image of the current group, the fp32 staging image of the next, the two B
+  // images, four all-zero limb rows and the read table (one word per walk position and tile row)
+  constexpr int TS_NT = OM == O_PHASE ? 4 : 16;
+  constexpr int TS_STG = BM * X3_ROWB, TS_B = TS_STG + BM * X3A_ROWB, TS_ZERO = TS_B + 2 * BN * X3_ROWB;
+  constexpr int TS_TOFF = TS_ZERO + 4 * X3_ROWB, TS_END = TS_TOFF + TS_NT * BM * 4;
+  constexpr int SMEMB =
+      ((V & X3_TAPSHARE) && TS_END > 2 * (BM + BN) * X3_ROWB) ? TS_END : 2 * (BM + BN) * X3_ROWB;
+  static_assert(SMEMB <= 160 * 1024 && TS_ZERO % 256 == 0, "the LDS of a CU; zero rows on the images' bank phase");
   // K tiles per MFMA accumulation block = the GEMM's sign block (GemmArgs::negk, a power of two >= 32)
   const int FLOG = __builtin_ctz((unsigned)p.negk >> 5), FLUSH = 1 << FLOG;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (BM + BN) * X3_ROWB];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[SMEMB];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -1483,15 +1493,17 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)(dst + 512 * 16 * j), 16, (int)aoff[j], ci0 * ESZ, 0, 0);
       next_ktile();
     };
+    // B image buf: at BOFF behind the start of buffer buf
+    constexpr int BOFF = TSHARE ? TS_B : BM * X3A_ROWB, BBUF = TSHARE ? BN * X3_ROWB : BUFB;
     auto dma_b = [&](int k0, int buf) {
-      unsigned char* dst = smem + buf * BUFB + BM * X3A_ROWB + wbase;
+      unsigned char* dst = smem + buf * BBUF + BOFF + wbase;
 #pragma unroll
       for (int j = 0; j < BJ; ++j)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_t)(dst + 512 * 16 * j), 16, (int)boff[j], k0 * 6, 0, 0);
     };
     const int fs = f32a_swz(lrow);
     const int ca0 = ((2 * loct) ^ fs) * 16, ca1 = ((2 * loct + 1) ^ fs) * 16;
-    const int arow = (wave * 32 + lrow) * X3A_ROWB, brow = BM * X3A_ROWB + lrow * X3_ROWB + oct16;
+    const int arow = (wave * 32 + lrow) * X3A_ROWB, brow = BOFF + lrow * X3_ROWB + oct16;
     auto rd_a = [&](const unsigned char* buf, f32x4 (&av)[2][2]) {
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
@@ -1524,20 +1536,31 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     // ---- X3_TAPSHARE: one image per group of four K tiles.  The launcher guarantees the slice-major walk, whole groups
     // per workgroup (K slices start at multiples of 4 K tiles), hwq | 256 with 64-row pieces a uniform stride apart
     // (x3_tapshare_ok), and the geometry of a ConvT phase (2 x 2, stride 1) or of its input gradient (4 x 4, stride 2,
-    // pad 1).  Image of local group G in the A half of buffer G & 1; piece j = rows 64 j .. 64 j + 63 (chunk id tid +
-    // 512 j).  DMA: this thread's chunk of the undisplaced pixel of row tid >> 3, pieces ts_pstr bytes apart, rows
-    // beyond M out of range.
-    // Behind each buffer's B image, two all-zero rows (one per row parity, ZREL): a padding tap reads the chunk it
-    // would read in a live row of its parity, so it takes that row's bank group and the lane group stays conflict-free.
-    // Behind the buffers, the read table (TOFF): for walk position pos and tile row r, the byte offset inside a buffer
-    // of the row tap(pos) reads for r -- image row r + delta(pos) with that row's swizzle applied to chunk 0, or the
-    // zero row -- built once per workgroup, so a tile's read addresses cost two ds_read_b32 and two VALU per lane
-    // instead of the mask test, the displacement and the swizzle (~30 VALU that found no MFMA gap)
-    constexpr int ZREL = BM * AROWB + BN * X3_ROWB, TOFF = 2 * BUFB, NT = OM == O_PHASE ? 4 : 16;
-    static_assert(!TSHARE || TOFF + NT * BM * 4 <= 2 * (BM + BN) * X3_ROWB, "no room for the read table");
+    // pad 1).
+    // The fp32 image of a group is staged once (TS_STG: 256 rows x 128 B, ts_swz; piece j = rows 64 j .. 64 j + 63,
+    // chunk id tid + 512 j; DMA: this thread's chunk of the undisplaced pixel of row tid >> 3, pieces ts_pstr bytes
+    // apart, rows beyond M out of range) and split into limbs once (round 9), into the limb image at LDS byte 0: row r
+    // = 192 B as three 64-B limb planes, octet q of limb l at l * 64 + (q ^ x3_swz(r)) * 16.  The four taps read their
+    // MFMA A fragments from it at rows r + delta(tap) -- the limbs the in-register split of each tap's fp32 rows gave,
+    // so the MFMA operands are bit for bit those of per-tap staging.  A row's slot (16-B bank group of ds_read_b128) is
+    // 4 ((l - r) & 3) + (q ^ x3_swz(r)): every lane group of a fragment read hits 16 distinct slots for every row
+    // rotation, and the 8-lane groups of the conversion's ds_write_b128 hit 8 distinct 16-B groups of their 32 banks.
+    // TS_ZERO: four all-zero limb rows, one per r & 3: a padding tap reads the chunk it would read in a live row of
+    // its residue, so it takes that row's slot and the lane group stays conflict-free.
+    // TS_TOFF, the read table: for walk position pos and tile row r, the LDS byte of limb 0, octet 0 ^ x3_swz of the
+    // row tap(pos) reads for r -- image row r + delta(pos), or the zero row -- built once per workgroup, so a tile's
+    // read addresses cost two ds_read_b32 and two v_xor per lane.
+    // Timeline of group G (K tiles 4 G .. 4 G + 3): the pieces of image G + 1 are DMA'd during tiles 4 G .. 4 G + 2 into
+    // the staging image (its last reader, the conversion of G during tile 4 G - 1, retired by that tile's barrier);
+    // during tile 4 G + 3 every thread reads its 16 staged values (the two octets it would read as fragments), splits
+    // them in that tile's MFMA gaps and writes the 6 limb octets over image G, whose last fragment reads (A(4 G + 3), one
+    // tile ahead) were in tile 4 G + 2; the barrier of 4 G + 3 publishes image G + 1.  Tile 4 G + 4 reads its own
+    // fragments at its start, as B's are read, and A(4 G + 5) during its MFMAs; sign blocks are whole groups
+    // (x3_tapshare_shape), so only a group's last tile flushes.
     unsigned ts_ibase = 0;
-    int ts_nv = 0, ts_pstr = 0, ts_o[2] = {0, 0};
+    int ts_nv = 0, ts_pstr = 0;
     if constexpr (TSHARE) {
+      constexpr int NT = TS_NT;
       const int r0 = tid >> 3, mi = m0 + r0;
       const unsigned b = mi / hwq, r = mi - b * hwq, qy = r / p.Wq, qx = r - qy * p.Wq;
       ts_ibase = ((b * p.Hin + qy * p.stride) * Win + qx * p.stride) * Cg * 4 + ((tid & 7) ^ ts_swz(r0)) * 16;
@@ -1560,9 +1583,9 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         const int R = row + dlt;
         const bool live = m < p.M && (unsigned)(y * p.stride - pad_y + ky) < (unsigned)p.Hin &&
                           (unsigned)(x * p.stride - pad_x + kx) < (unsigned)Win && (unsigned)R < (unsigned)BM;
-        reinterpret_cast<int*>(smem + TOFF)[id] = (live ? R * X3A_ROWB : ZREL + (R & 1) * X3A_ROWB) + ts_swz(R) * 16;
+        reinterpret_cast<int*>(smem + TS_TOFF)[id] = (live ? R * X3_ROWB : TS_ZERO + (R & 3) * X3_ROWB) + x3_swz(R) * 16;
       }
-      if (tid < 128) reinterpret_cast<float*>(smem + (tid >> 6) * BUFB + ZREL)[tid & 63] = 0.f;
+      if (tid < 4 * X3_ROWB / 4) reinterpret_cast<float*>(smem + TS_ZERO)[tid] = 0.f;
     }
     // piece j of local group G: global group gg = (slice, class) for the 4 x 4 conv (class c = taps of parity (c >> 1,
     // c & 1), reading the pixels of the opposite parity), slice for a ConvT phase
@@ -1574,118 +1597,53 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         sl = gg >> 2;
         coff = ((1 - (c >> 1)) * Win + (1 - (c & 1))) * Cg * 4;
       }
-      unsigned char* dst = smem + (G & 1) * BUFB + wbase + 512 * 16 * j;
+      unsigned char* dst = smem + TS_STG + wbase + 512 * 16 * j;
       const int vo = j < ts_nv ? (int)(ts_ibase + (unsigned)(j * ts_pstr)) : (int)KM_OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)dst, 16, vo, sl * (X3_BK * 4) + coff, 0, 0);
     };
-    // ts_o: the LDS byte addresses of this lane's two fragment rows (chunk 2 loct; chunk 2 loct + 1 is at ^ 16) of
-    // local K tile ktn, from the table; every address is an image row or a zero row of the tile's buffer
-    const int ts_tb = TOFF + (wave * 32 + lrow) * 4;
-    auto ts_addr = [&](int ktn) {
-      const int ta = ts_tb + ((kt0 + ktn) & (NT - 1)) * (BM * 4), ib = ((ktn >> 2) & 1) * BUFB;
+    // the LDS byte addresses (limb 0; limb l is 64 l further) of this lane's two fragment rows of local K tile ktn, from
+    // the table; every address is an image row or a zero row
+    const int ts_tb = TS_TOFF + (wave * 32 + lrow) * 4;
+    auto ts_addr = [&](int ktn, int (&o)[2]) {
+      const int ta = ts_tb + ((kt0 + ktn) & (TS_NT - 1)) * (BM * 4);
 #pragma unroll
-      for (int a = 0; a < 2; ++a) ts_o[a] = (*reinterpret_cast<const int*>(smem + ta + a * 64) ^ (loct << 5)) + ib;
+      for (int a = 0; a < 2; ++a) o[a] = *reinterpret_cast<const int*>(smem + ta + a * 64) ^ (loct << 4);
     };
-    auto rd_a_ts = [&](f32x4 (&av)[2][2]) {
+    auto rd_limb = [&](const int (&o)[2], bf16x8 (&f)[2][3], int a, int l) {
+      f[a][l] = *reinterpret_cast<const bf16x8*>(smem + o[a] + l * 64);
+    };
+    // the conversion: this lane's two octets (rows wave * 32 + 16 a + lrow, octet loct) of the staging image ...
+    const int cv_rd = TS_STG + (wave * 32 + lrow) * X3A_ROWB + ((2 * loct) ^ ts_swz(lrow)) * 16;
+    auto rd_stg = [&](f32x4 (&av)[2][2]) {
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
-        av[a][0] = *reinterpret_cast<const f32x4*>(smem + ts_o[a]);
-        av[a][1] = *reinterpret_cast<const f32x4*>(smem + (ts_o[a] ^ 16));
+        av[a][0] = *reinterpret_cast<const f32x4*>(smem + cv_rd + a * 16 * X3A_ROWB);
+        av[a][1] = *reinterpret_cast<const f32x4*>(smem + (cv_rd ^ 16) + a * 16 * X3A_ROWB);
       }
     };
+    // ... and their limbs into the limb image
+    const int cv_wr = (wave * 32 + lrow) * X3_ROWB + (loct ^ sw) * 16;
+    auto wr_limb = [&](const bf16x8 (&f)[2][3], int a) {
+#pragma unroll
+      for (int l = 0; l < 3; ++l) *reinterpret_cast<bf16x8*>(smem + cv_wr + a * 16 * X3_ROWB + l * 64) = f[a][l];
+    };
     bf16x8 fx[2][3], fy[2][3], fb[2][3];
-    if constexpr (TSHARE) {
-      if (nk > 0) {
+    constexpr int SG_MFMA = 0x8, SG_VALU = 0x2, SG_DS_RD = 0x100, SG_DS_WR = 0x200;
+    auto mfma6 = [&](const bf16x8 (&fc)[2][3], int t) {  // B tile t (slot t & 1) against both A tiles
+      const int sl = t & 1;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) dma_img(0, j);
-        dma_b(kbeg, 0);
+      for (int a = 0; a < 2; ++a) {
+        f32x4 c = acc16[2 * a + (t >> 2)][t & 3];
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][2], fb[sl][0], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][1], fb[sl][1], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][0], fb[sl][2], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][1], fb[sl][0], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][0], fb[sl][1], c, 0, 0, 0);
+        acc16[2 * a + (t >> 2)][t & 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][0], fb[sl][0], c, 0, 0, 0);
       }
-      if (nk > 4) dma_img(1, 0);
-      __syncthreads();
-      f32x4 av0[2][2];
-      ts_addr(0);
-      rd_a_ts(av0);
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) split2(av0, fx, a, e);
-      ts_addr(1);
-    } else {
-      if (nk > 0) {
-        dma_a(0);
-        dma_b(kbeg, 0);
-      }
-      if (nk > 1) dma_a(1);
-      __syncthreads();
-      rd_split(smem, fx);
-    }
-    constexpr int SG_MFMA = 0x8, SG_VALU = 0x2, SG_DS_RD = 0x100;
-    auto tile = [&](int kt, bf16x8 (&fc)[2][3], bf16x8 (&fn)[2][3]) {
-      const unsigned char* base = smem + (kt & 1) * BUFB;
-      if (kt + 1 < nk) dma_b(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1);
-      if constexpr (TSHARE) {
-        // one piece of the next group's image per tile: group G = (kt + 1) / 4 + 1 over tiles 4 G - 5 .. 4 G - 2, into
-        // the buffer whose last read (A(4 G - 5), by tile 4 G - 6) the previous barrier retired; its fourth piece lands
-        // at the barrier of tile 4 G - 2, one tile before A(4 G) is read
-        const int G = ((kt + 1) >> 2) + 1;
-        if (4 * G < nk) dma_img(G, (kt + 1) & 3);
-      } else if (kt + 2 < nk) {
-        dma_a(kt & 1);
-      }
-      // A(kt + 1): read and split unconditionally (past the last tile it is stale, in-bounds LDS, never used); two
-      // elements per B tile, in that tile's MFMA gaps
-      f32x4 av[2][2];
-      if constexpr (TSHARE)
-        rd_a_ts(av);  // (addresses from the previous tile)
-      else
-        rd_a(smem + ((kt + 1) & 1) * BUFB, av);
-      auto rd_b = [&](int t, int slot) {
-#pragma unroll
-        for (int l = 0; l < 3; ++l) fb[slot][l] = *reinterpret_cast<const bf16x8*>(base + brow + t * 16 * X3_ROWB + l * 16);
-      };
-      rd_b(0, 0);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        if (t + 1 < 8) rd_b(t + 1, (t + 1) & 1);
-        if constexpr (TSHARE) {
-          if (t == 1) ts_addr(kt + 2);  // A(kt + 2)'s read addresses, one tile ahead of their use
-        }
-        const int sl = t & 1;
-        split2(av, fn, t >> 2, (t & 3) * 2);
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          f32x4 c = acc16[2 * a + (t >> 2)][t & 3];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][2], fb[sl][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][1], fb[sl][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][0], fb[sl][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][1], fb[sl][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][0], fb[sl][1], c, 0, 0, 0);
-          acc16[2 * a + (t >> 2)][t & 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[a][0], fb[sl][0], c, 0, 0, 0);
-        }
-      }
-      // schedule: the 4 A reads and B tiles 0 and 1 (6 reads) first, then per B tile t its 12 MFMAs with the split's
-      // VALU in their gaps, then B tile t + 2's reads (into the slot tile t's MFMAs just released)
-      __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 10, 0);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-#pragma unroll
-        for (int m = 0; m < 12; ++m) {
-          __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
-        }
-        if (t + 2 < 8) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-        if constexpr (TSHARE) {
-          if (t == 0) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 2, 0);  // the two table reads
-        }
-      }
-      // the next tile's limbs are complete before the barrier: otherwise the compiler sinks the split into the next
-      // tile, where it runs ahead of the first MFMAs instead of in this tile's gaps
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int l = 0; l < 3; ++l) asm volatile("" : "+v"(fn[a][l]));
-      __syncthreads();
-      if (((kt + 1) & (FLUSH - 1)) != 0) return;
+    };
+    // the end of a sign block after the MFMAs of K tile kt: into the register slab (KREG) or the block total
+    auto flush_blk = [&](int kt) {
       if constexpr (KREG) {
         // the register slab layout of the 4 x 2 wave grid (x3_ksplit_reduce_tile_kernel): A tile a of this wave is
         // row tile (w & 1) * 2 + a of wave row w >> 1, B tile t is column tile t & 3 of wave column t >> 2
@@ -1720,9 +1678,145 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         flush16(kt);
       }
     };
-    for (int kt = 0; kt < nk; kt += 2) {  // two tiles per trip: the limb sets trade roles without register moves
-      tile(kt, fx, fy);
-      if (kt + 1 < nk) tile(kt + 1, fy, fx);
+    if constexpr (TSHARE) {
+      int oa[2], ob[2];  // fragment read addresses, two K tiles in flight
+      if (nk > 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dma_img(0, j);
+        dma_b(kbeg, 0);
+      }
+      __syncthreads();  // the table, the zero rows, the staged image 0, B(0)
+      {
+        f32x4 av0[2][2];
+        rd_stg(av0);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+          for (int e = 0; e < 8; e += 2) split2(av0, fx, a, e);
+          wr_limb(fx, a);
+        }
+      }
+      ts_addr(0, oa);
+      ts_addr(1, ob);
+      __syncthreads();  // limb image 0
+      // K tile kt = position PH of its group; fc: its A limbs (PH 0 reads them first), fn: A(kt + 1)'s, read through
+      // on (PH 0-2), or the conversion's (PH 3); of: receives A(kt + 2)'s addresses (PH 0 reads its own through it first)
+      auto tile = [&](int kt, auto PH_, bf16x8 (&fc)[2][3], bf16x8 (&fn)[2][3], int (&on)[2], int (&of)[2]) {
+        constexpr int PH = decltype(PH_)::value;
+        const unsigned char* base = smem + (PH & 1) * BBUF;  // groups start at even local tiles
+        if (kt + 1 < nk) dma_b(kbeg + (kt + 1) * X3_BK, (PH + 1) & 1);
+        if constexpr (PH < 3) {  // the next group's image: pieces 0 and 1, 2, 3
+          const int G = (kt >> 2) + 1;
+          if (4 * G < nk) {
+            if constexpr (PH == 0) dma_img(G, 0);
+            dma_img(G, PH + 1);
+          }
+        }
+        auto rd_b = [&](int t, int slot) {
+#pragma unroll
+          for (int l = 0; l < 3; ++l) fb[slot][l] = *reinterpret_cast<const bf16x8*>(base + brow + t * 16 * X3_ROWB + l * 16);
+        };
+        f32x4 av[2][2];
+        if constexpr (PH == 0) {
+#pragma unroll
+          for (int i = 0; i < 6; ++i) rd_limb(of, fc, i / 3, i % 3);
+        }
+        // (past the last group the conversion reads a stale, in-bounds staging image into an image nobody reads)
+        if constexpr (PH == 3) rd_stg(av);
+        rd_b(0, 0);
+        rd_b(1, 1);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          if constexpr (PH == 3) split2(av, fn, t >> 2, (t & 3) * 2);
+          mfma6(fc, t);
+          if (t + 2 < 8) rd_b(t + 2, t & 1);
+          if constexpr (PH < 3) {
+            if (t < 6) rd_limb(on, fn, t / 3, t % 3);
+          }
+          if (t == 0) ts_addr(kt + 2, of);
+          if constexpr (PH == 3) {
+            if (t == 4) wr_limb(fn, 0);
+            if (t == 7) wr_limb(fn, 1);
+          }
+        }
+        // schedule: this tile's own A reads (PH 0) or the staged values (PH 3) and B tiles 0 and 1 first, then per B tile
+        // t its 12 MFMAs (PH 3: the split's VALU in their gaps), then the reads and writes written behind them above
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, PH == 0 ? 12 : PH == 3 ? 10 : 6, 0);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+#pragma unroll
+          for (int m = 0; m < 12; ++m) {
+            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+            if constexpr (PH == 3) __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
+          }
+          if (t + 2 < 8) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+          if (PH < 3 && t < 6) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 1, 0);
+          if (t == 0) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 2, 0);  // the two table reads
+          if (PH == 3 && (t == 4 || t == 7)) __builtin_amdgcn_sched_group_barrier(SG_DS_WR, 3, 0);
+        }
+        __syncthreads();
+        if constexpr (PH == 3) {
+          if (((kt + 1) & (FLUSH - 1)) == 0) flush_blk(kt);
+        }
+      };
+      for (int kt = 0; kt < nk; kt += 4) {  // one group per trip: the limb sets and address pairs trade roles in place
+        tile(kt, std::integral_constant<int, 0>{}, fx, fy, ob, oa);
+        tile(kt + 1, std::integral_constant<int, 1>{}, fy, fx, oa, ob);
+        tile(kt + 2, std::integral_constant<int, 2>{}, fx, fy, ob, oa);
+        tile(kt + 3, std::integral_constant<int, 3>{}, fy, fx, ob, ob);
+      }
+    } else {
+      if (nk > 0) {
+        dma_a(0);
+        dma_b(kbeg, 0);
+      }
+      if (nk > 1) dma_a(1);
+      __syncthreads();
+      rd_split(smem, fx);
+      auto tile = [&](int kt, bf16x8 (&fc)[2][3], bf16x8 (&fn)[2][3]) {
+        const unsigned char* base = smem + (kt & 1) * BUFB;
+        if (kt + 1 < nk) dma_b(kbeg + (kt + 1) * X3_BK, (kt + 1) & 1);
+        if (kt + 2 < nk) dma_a(kt & 1);
+        // A(kt + 1): read and split unconditionally (past the last tile it is stale, in-bounds LDS, never used); two
+        // elements per B tile, in that tile's MFMA gaps
+        f32x4 av[2][2];
+        rd_a(smem + ((kt + 1) & 1) * BUFB, av);
+        auto rd_b = [&](int t, int slot) {
+#pragma unroll
+          for (int l = 0; l < 3; ++l) fb[slot][l] = *reinterpret_cast<const bf16x8*>(base + brow + t * 16 * X3_ROWB + l * 16);
+        };
+        rd_b(0, 0);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          if (t + 1 < 8) rd_b(t + 1, (t + 1) & 1);
+          split2(av, fn, t >> 2, (t & 3) * 2);
+          mfma6(fc, t);
+        }
+        // schedule: the 4 A reads and B tiles 0 and 1 (6 reads) first, then per B tile t its 12 MFMAs with the split's
+        // VALU in their gaps, then B tile t + 2's reads (into the slot tile t's MFMAs just released)
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 10, 0);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+#pragma unroll
+          for (int m = 0; m < 12; ++m) {
+            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
+          }
+          if (t + 2 < 8) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+        }
+        // the next tile's limbs are complete before the barrier: otherwise the compiler sinks the split into the next
+        // tile, where it runs ahead of the first MFMAs instead of in this tile's gaps
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int l = 0; l < 3; ++l) asm volatile("" : "+v"(fn[a][l]));
+        __syncthreads();
+        if (((kt + 1) & (FLUSH - 1)) == 0) flush_blk(kt);
+      };
+      for (int kt = 0; kt < nk; kt += 2) {  // two tiles per trip: the limb sets trade roles without register moves
+        tile(kt, fx, fy);
+        if (kt + 1 < nk) tile(kt + 1, fy, fx);
+      }
     }
   } else {
     // ---- the limb A image (X3_BASE alone, X3_WIDE, X3_KREG; the only O_WGRAD path): each wave 4 x 4 tiles of 16 x 16
