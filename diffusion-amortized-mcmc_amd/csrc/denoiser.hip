@@ -29,6 +29,7 @@
 #include <mutex>
 #include <vector>
 
+#include "denoiser_rows.h"
 #include "gemm.h"
 
 namespace {
@@ -1579,9 +1580,14 @@ __global__ void copy_kernel(const float* src, float* dst, long n) {
   if (i < n) dst[i] = src[i];
 }
 
+// a block's columns in the per-(step, row) tables (ctx, gate | hyper bias): its dout, up to a multiple of 4 so every
+// block starts float4-aligned (only out2 of a denoiser with nz % 4 != 0 is padded: the row-resident form)
+inline int lay_dout(int dout) { return (dout + 3) & ~3; }
+inline bool narrow_out2(const damc_denoiser_t* d) { return (d->nz & 3) != 0; }
+
 int sum_dout(const damc_denoiser_t* d) {
   int s = 0;
-  for (int j = 0; j < 7; ++j) s += d->blocks[j].dout;
+  for (int j = 0; j < 7; ++j) s += lay_dout(d->blocks[j].dout);
   return s;
 }
 
@@ -1631,13 +1637,23 @@ size_t carve(const damc_denoiser_t* d, int B, int n, char* base, SweepWs* w) {
   t.z = take((long)B * d->nz);
   for (int j = 0; j < 7; ++j) t.outs[j] = take((long)B * d->blocks[j].dout);
   t.call = reinterpret_cast<SweepCall*>(take(64));
-  t.ring = take((long)n * B * S);
-  t.zring = take((long)(n + 1) * B * d->nz);
+  // (the team sweep's rings: never used by a shape only the row-resident form takes)
+  t.ring = take(narrow_out2(d) ? 0 : (long)n * B * S);
+  t.zring = take(narrow_out2(d) ? 0 : (long)(n + 1) * B * d->nz);
   t.tab = take(8L * n);
   t.err = reinterpret_cast<int*>(take(1));
   t.bytes = off;
   if (w) *w = t;
   return off;
+}
+
+// the row-resident form's LDS image (denoiser_rows.hip) of 16 rows
+int rows_ld(const damc_denoiser_t* d, damc::RowsBlock* b) {
+  damc::RowsBlock tmp[7];
+  return damc::rows_layout(d->nz, d->blocks[0].dout, kpad(2 * d->nz), b ? b : tmp);
+}
+bool rows_fit(const damc_denoiser_t* d) {
+  return (size_t)damc::ROWS_TM * rows_ld(d, nullptr) * sizeof(float) <= damc::ROWS_LDS_MAX;
 }
 
 int validate(const damc_denoiser_t* d) {
@@ -1652,11 +1668,21 @@ int validate(const damc_denoiser_t* d) {
     const damc_csq_block_t& b = d->blocks[j];
     if (b.din != din[j] || b.dout != dout[j]) return DAMC_ERR_ARG;
     if (!b.wl || !b.bl || !b.ws || !b.bs || !b.wg || !b.bg || !b.wb || !d->wctx[j] || !d->bctx[j]) return DAMC_ERR_ARG;
-    // float4 fragments / staging need every width % 4 == 0; the in0 LDS image must fit
-    if ((b.din & 3) || (b.dout & 3) || (nz & 3)) return DAMC_ERR_UNSUPPORTED;
+    // float4 fragments / staging need every width % 4 == 0 (out2's dout = nz aside: the row-resident form takes any
+    // even nz); the in0 LDS image must fit
+    if ((b.din & 3) || (j < 6 && (b.dout & 3))) return DAMC_ERR_UNSUPPORTED;
   }
   if (nz > 16 * EMB_G) return DAMC_ERR_UNSUPPORTED;
+  // nz % 4 != 0: the per-call stages run blocks 0-5 on the skinny GEMM and out2 on its own small kernels, and the
+  // chain runs row-resident, which must fit its LDS image
+  if (narrow_out2(d) && ((d->ntemb & 15) || (d->nxemb & 3) || (w & 15) || !rows_fit(d))) return DAMC_ERR_UNSUPPORTED;
   return 0;
+}
+
+// DAMC_SWEEP_ROWS=1 (read per call): the row-resident form for every shape
+bool rows_forced() {
+  const char* e = getenv("DAMC_SWEEP_ROWS");
+  return e && e[0] == '1';
 }
 
 struct Launch {
@@ -2289,6 +2315,7 @@ extern "C" long damc_sweep_team_failures(int device) {
 
 extern "C" size_t damc_sweep_workspace_bytes(const damc_denoiser_t* d, int B, int n) {
   if (validate(d) || B <= 0 || n <= 0) return 0;
+  if (rows_forced() && !rows_fit(d)) return 0;
   return carve(d, B, n, nullptr, nullptr);
 }
 
@@ -2310,8 +2337,14 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   int coloff[7];
   for (int j = 0, o = 0; j < 7; ++j) {
     coloff[j] = o;
-    o += d->blocks[j].dout;
+    o += lay_dout(d->blocks[j].dout);
   }
+  // nz % 4 != 0: out2 (dout = nz) is off the float4 paths of stages 2 and 3; they run blocks 0 .. nb - 1 as they run
+  // every other denoiser's, and out2's columns come from the narrow kernels of denoiser_rows.hip
+  const bool narrow = narrow_out2(d);
+  const int nb = narrow ? 6 : 7;
+  const bool rows = narrow || rows_forced();
+  if (rows && !rows_fit(d)) return DAMC_ERR_UNSUPPORTED;
 
   // ---- 1. pack the live weights
   {
@@ -2348,7 +2381,7 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
     pa.bctx = w.bctx;
     // the skinny precompute GEMMs read the time MLP and ctx Linears in their PyTorch layouts: no transposes
     bool sk = (nt & 15) == 0 && (nx & 3) == 0;
-    for (int j = 0; j < 7; ++j) sk = sk && (d->blocks[j].dout & 15) == 0;
+    for (int j = 0; j < nb; ++j) sk = sk && (d->blocks[j].dout & 15) == 0;
     hipLaunchKernelGGL(pack_denoiser_kernel, dim3((unsigned)((maxn + 255) / 256), 7, sk ? 2 : 3), dim3(256), 0, s, pa);
     const long ntt = (long)nt * nt;
     if (!sk) {
@@ -2363,7 +2396,8 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
 
   // ---- 2. ctx: time MLP (n rows), xemb part (B rows), c for every (step, row)
   bool skinny = (nt & 15) == 0 && (nx & 3) == 0;
-  for (int j = 0; j < 7; ++j) skinny = skinny && (d->blocks[j].dout & 15) == 0;
+  for (int j = 0; j < nb; ++j) skinny = skinny && (d->blocks[j].dout & 15) == 0;
+  if (narrow && !skinny) return DAMC_ERR_UNSUPPORTED;  // (validate() has checked)
   if (skinny) {
     SkArgs g;
     memset(&g, 0, sizeof(g));
@@ -2383,9 +2417,9 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
     g.Y = w.t2;  // the ctx Linear consumes SiLU(temb)
     if ((rc = launch_skinny(g, "sweep_pre", s))) return rc;
     g.A = w.t2;
-    g.N = S;
-    g.nseg = 7;
-    for (int j = 0; j < 7; ++j) g.seg[j] = SkSeg{d->wctx[j], d->bctx[j], (long)nt + nx, coloff[j]};
+    g.N = narrow ? coloff[6] : S;
+    g.nseg = nb;
+    for (int j = 0; j < nb; ++j) g.seg[j] = SkSeg{d->wctx[j], d->bctx[j], (long)nt + nx, coloff[j]};
     g.silu_y = 0;
     g.Y = w.qt;
     g.ldy = S;
@@ -2394,10 +2428,19 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
     g.lda = nx;
     g.M = B;
     g.K = nx;
-    for (int j = 0; j < 7; ++j) g.seg[j] = SkSeg{d->wctx[j] + nt, nullptr, (long)nt + nx, coloff[j]};
+    for (int j = 0; j < nb; ++j) g.seg[j] = SkSeg{d->wctx[j] + nt, nullptr, (long)nt + nx, coloff[j]};
     g.silu_a = 1;
     g.Y = w.px;
     if ((rc = launch_skinny(g, "sweep_pre", s))) return rc;
+    if (narrow) {  // out2's columns of qt and px (its padding columns zero)
+      const int d6 = d->blocks[6].dout, p6 = lay_dout(d6);
+      if ((rc = damc::launch_narrow_linear(w.t2, nt, n, nt, 0, d->wctx[6], (long)nt + nx, d->bctx[6], d6, p6,
+                                           w.qt + coloff[6], S, s)))
+        return rc;
+      if ((rc = damc::launch_narrow_linear(xemb, nx, B, nx, 1, d->wctx[6] + nt, (long)nt + nx, nullptr, d6, p6,
+                                           w.px + coloff[6], S, s)))
+        return rc;
+    }
     if ((rc = launch_ctx(w.px, w.qt, n, B, S, w.cx, s))) return rc;
   } else {
     damc::GemmArgs g;
@@ -2455,7 +2498,7 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   // ---- 3. every block's gate and hyper bias for every (step, row): [sigmoid(c Wg^T + bg) | c Wb^T]
   damc::GemmArgs hg[7];
   double hflops = 0.0;
-  for (int j = 0; j < 7; ++j) {
+  for (int j = 0; j < nb; ++j) {
     const int dout = d->blocks[j].dout;
     damc::GemmArgs& g = hg[j];
     g.M = n * B;
@@ -2479,12 +2522,12 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   bool hy_ok = !(hye && strcmp(hye, "fp32") == 0) && (S % 4 == 0) && ((uintptr_t)w.cx % 16 == 0) &&
                ((uintptr_t)w.gh % 16 == 0);
   HyperGroup hgp{};
-  hgp.n = 7;
+  hgp.n = nb;
   {
     const char* hs = getenv("DAMC_SWEEP_HYPER_SIGMOID");  // (read per call) exact: IEEE expf and division
     hgp.exact_sig = hs && strcmp(hs, "exact") == 0;
   }
-  for (int j = 0; j < 7 && hy_ok; ++j) {
+  for (int j = 0; j < nb && hy_ok; ++j) {
     const damc_csq_block_t& bk = d->blocks[j];
     const int dout = bk.dout;
     hy_ok = dout % 32 == 0 && dout <= HY_NTMAX * HY_KT && bk.wg && bk.wb && (uintptr_t)bk.wg % 16 == 0 &&
@@ -2520,10 +2563,10 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
     rc = (int)hipGetLastError();
   } else {
     rc = (hge && atoi(hge) == 0) ? DAMC_ERR_UNSUPPORTED
-                                 : damc::launch_gemm_group(hg, 7, damc::EPI_GATE, "sweep_hyper", hflops, s);
+                                 : damc::launch_gemm_group(hg, nb, damc::EPI_GATE, "sweep_hyper", hflops, s);
   }
   if (rc == DAMC_ERR_UNSUPPORTED) {
-    for (int j = 0; j < 7; ++j) {
+    for (int j = 0; j < nb; ++j) {
       const int dout = d->blocks[j].dout;
       if ((rc = damc::launch_gemm(hg[j], damc::A_DENSE, damc::EPI_GATE, damc::O_DENSE, 1, "sweep_hyper",
                                   2.0 * n * B * dout * 2.0 * dout, s)))
@@ -2532,8 +2575,52 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   } else if (rc) {
     return rc;
   }
+  if (narrow) {  // out2's gate and hyper bias (K = N = nz), with the exact sigmoid
+    const damc_csq_block_t& bk = d->blocks[6];
+    if ((rc = damc::launch_narrow_hyper(w.cx + coloff[6], S, (long)n * B, bk.dout, bk.wg, bk.bg, bk.wb,
+                                        w.gh + 2 * coloff[6], 2L * S, s)))
+      return rc;
+  }
 
   // ---- 4. the dependent chain
+  if (rows) {
+    // row-resident (denoiser_rows.hip): one launch, each workgroup runs every step and block of its 16 rows on the
+    // caller's zt in place; the call's values travel in the kernel arguments
+    damc::RowsArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.ld = rows_ld(d, ra.b);
+    for (int j = 0; j < 7; ++j) {
+      const damc_csq_block_t& bk = d->blocks[j];
+      damc::RowsBlock& p = ra.b[j];
+      p.w = w.w[j];
+      p.bls = w.bls[j];
+      p.din = bk.din;
+      p.kp = kpad(bk.din);
+      p.dout = bk.dout;
+      p.ntn = (bk.dout + TC - 1) / TC;
+      p.ghoff = 2 * coloff[j];
+    }
+    ra.bmat = w.bmat;
+    ra.nz = d->nz;
+    ra.B = B;
+    ra.n = n;
+    ra.residual = d->residual;
+    ra.gh = w.gh;
+    ra.ldgh = 2L * S;
+    ra.zt = zt;
+    ra.noise = (with_noise && noise) ? noise : nullptr;
+    ra.eps_log = eps_log;
+    ra.eps_log_steps = eps_log ? eps_log_steps : 0;
+    ra.seed = seed;
+    ra.chain_base = chain_base;
+    ra.step_offset = step_offset;
+    ra.with_noise = with_noise ? 1 : 0;
+    if ((rc = step_table(coef, n, s, &ra.tab))) return rc;
+    double fl = 0;
+    for (int j = 0; j < 7; ++j) fl += 2.0 * B * 2.0 * d->blocks[j].din * d->blocks[j].dout;
+    ProfScope ps("denoise_chain", fl * n, s);
+    return damc::launch_sweep_rows(ra, s);
+  }
   SweepCall call;
   call.noise = (with_noise && noise) ? noise : nullptr;
   call.eps_log = eps_log;

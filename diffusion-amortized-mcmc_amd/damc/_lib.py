@@ -19,6 +19,7 @@ ENGINE_LIMB, ENGINE_FP32 = 0, 1
 DAMC_ERR_ARG, DAMC_ERR_WORKSPACE, DAMC_ERR_UNSUPPORTED = 1001, 1002, 1003
 LAYER_PROJ, LAYER_UP2, LAYER_SMALLC, LAYER_LINEAR = 1, 2, 3, 4
 ACT_NONE, ACT_LRELU, ACT_TANH = 0, 1, 2
+ACT_RELU = 4  # damc_mlp_forward
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 
@@ -115,6 +116,18 @@ class PriorEmbGrads(ctypes.Structure):  # damc_prior_emb_grads_t
     _fields_ = [(k, ctypes.c_void_p) for k in ("w1", "b1", "w2", "b2")]
 
 
+MLP_MAX_LAYERS, MLP_MAX_WIDTH = 8, 256
+
+
+class MlpLayer(ctypes.Structure):  # damc_mlp_layer_t
+    _fields_ = [("din", ctypes.c_int), ("dout", ctypes.c_int), ("act", ctypes.c_int), ("slope", ctypes.c_float),
+                ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p)]
+
+
+class Mlp(ctypes.Structure):  # damc_mlp_t
+    _fields_ = [("n_layers", ctypes.c_int), ("layers", MlpLayer * MLP_MAX_LAYERS)]
+
+
 class AdamHparams(ctypes.Structure):
     _fields_ = [("neg_step_size", ctypes.c_float), ("one_minus_beta1", ctypes.c_float), ("beta2", ctypes.c_float),
                 ("one_minus_beta2", ctypes.c_float), ("bc2_sqrt", ctypes.c_float), ("eps", ctypes.c_float),
@@ -190,6 +203,7 @@ _SIGS = {
     "damc_q_encoder_workspace_bytes": (_SZ, [ctypes.POINTER(Encoder), _I]),
     "damc_q_encoder_fwd": (_I, [ctypes.POINTER(Encoder), _P, _I, _P, _P, _SZ, _P]),
     "damc_gemm": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "damc_mlp_forward": (_I, [ctypes.POINTER(Mlp), _P, _I, _P, _P]),
     "damc_conv2d_x3_bytes": (_SZ, [_I, _I, _I]),
     "damc_x3_sign_block": (_I, []),
     "damc_x3_layer_sign_block": (_I, [ctypes.POINTER(Layer), _I]),

@@ -4,6 +4,8 @@ Mirrors ``_netQ_U.forward`` (workspace/src/diffusion_net.py:585-622):
   x given : xemb = encoder(x)                 -> Encoder_* on the MFMA conv engine + fused IN/LReLU
   x None  : xemb = prior_emb(randn(b, nz))    -> two GEMMs (LeakyReLU 0.01 between)
   zt = randn(b, nz) (host generator, as the reference) then n_interval reverse steps in libdamc.
+The toy's _netQ_U_toy (workspace/toy_example/src/diffusion_net.py:141-239) takes the same route: its MLP encoder and
+its prior_emb (nz = 2) run as one fused launch (damc_mlp_forward), its sweep in the library's row-resident form.
 
 The per-step schedule scalars (logsnr_t/logsnr_s and the coefficients of pred_x_from_eps /
 diffusion_reverse, diffusion_helper_func.py:36-70) and the sinusoidal time embedding input
@@ -244,7 +246,59 @@ _ENC = weakref.WeakKeyDictionary()
 _DEN = weakref.WeakKeyDictionary()
 
 
+def mlp_desc(seq, device):
+    """An nn.Sequential of Linear / ReLU / LeakyReLU as a damc_mlp_t over its live parameters (the toy's encoder and
+    prior_emb, workspace/toy_example/src/diffusion_net.py:166-184).  Returns (descriptor, tensors to keep alive)."""
+    d = _lib.Mlp()
+    keep, n = [], 0
+    mods = list(seq)
+    i = 0
+    while i < len(mods):
+        lin = mods[i]
+        if not isinstance(lin, torch.nn.Linear) or hasattr(lin, "weight_orig"):
+            raise NotImplementedError("unexpected MLP module %r" % (lin,))
+        if n >= _lib.MLP_MAX_LAYERS or max(lin.in_features, lin.out_features) > _lib.MLP_MAX_WIDTH:
+            raise NotImplementedError("MLP with more than %d layers or a width over %d"
+                                      % (_lib.MLP_MAX_LAYERS, _lib.MLP_MAX_WIDTH))
+        act, slope = _lib.ACT_NONE, 0.0
+        if i + 1 < len(mods) and not isinstance(mods[i + 1], torch.nn.Linear):
+            a = mods[i + 1]
+            if isinstance(a, torch.nn.ReLU):
+                act = _lib.ACT_RELU
+            elif isinstance(a, torch.nn.LeakyReLU):
+                act, slope = _lib.ACT_LRELU, float(a.negative_slope)
+            else:
+                raise NotImplementedError("unexpected MLP activation %r" % (a,))
+            i += 1
+        i += 1
+        w = _dev(lin.weight, device)
+        b = _dev(lin.bias, device) if lin.bias is not None else None
+        e = d.layers[n]
+        e.din, e.dout, e.act, e.slope = lin.in_features, lin.out_features, act, slope
+        e.w, e.bias = ptr(w), ptr(b)
+        keep += [w, b]
+        n += 1
+    d.n_layers = n
+    return d, keep
+
+
+def mlp_forward(seq, x):
+    """seq(x) for an nn.Sequential of Linear / ReLU / LeakyReLU in one damc_mlp_forward launch (no autograd)."""
+    x = x.detach().to(dtype=torch.float32).contiguous()
+    if x.device.type != "cuda":
+        raise _lib.DamcError("MLP input must be on a ROCm device; the HIP path has no CPU fallback")
+    d, keep = mlp_desc(seq, x.device)
+    if x.dim() != 2 or x.shape[1] != d.layers[0].din:
+        raise _lib.DamcError("MLP input must be (batch, %d)" % d.layers[0].din)
+    out = torch.empty(x.shape[0], d.layers[d.n_layers - 1].dout, dtype=torch.float32, device=x.device)
+    check(_lib.lib().damc_mlp_forward(ctypes.byref(d), ptr(x), x.shape[0], ptr(out), _lib.stream_ptr(x.device)),
+          "damc_mlp_forward")
+    return out
+
+
 def encoder_forward(enc, x):
+    if isinstance(enc, torch.nn.Sequential):  # the toy's MLP encoder (workspace/toy_example/src/diffusion_net.py:166-174)
+        return mlp_forward(enc, x)
     plan = _ENC.get(enc)
     if plan is None:
         plan = _ENC[enc] = EncoderPlan(enc)
@@ -256,6 +310,8 @@ def encoder_forward(enc, x):
 
 def prior_embedding(Q, noise):
     """prior_emb = Linear(nz,128) -> LeakyReLU(0.01) -> Linear(128,nxemb) (diffusion_net.py:577-581)."""
+    if Q.nz % 4:  # K = nz off the GEMM's float4 rows (the toy, nz = 2): the fused MLP
+        return mlp_forward(Q.prior_emb, noise)
     L = _lib.lib()
     dev = noise.device
     stream = _lib.stream_ptr(dev)
@@ -306,6 +362,9 @@ def q_forward(Q, x=None, b=None, device=None, cond_w=-1, zt=None, seed=None, cha
     global index of row 0 — a shard that passes its slice of the global zt, the global seed and its slice
     start reproduces its rows of the 1-GPU sweep bit for bit."""
     if cond_w is not None and cond_w > 0 and x is not None:
+        if Q.nz % 4:
+            raise NotImplementedError("classifier-free guidance (cond_w > 0) is not implemented for nz % 4 != 0 "
+                                      "(the toy amortizer): the guided step loop runs on the training kernels")
         return _q_forward_guided(Q, x, float(cond_w))
     if x is not None:
         assert b is None and device is None

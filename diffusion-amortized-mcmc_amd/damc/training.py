@@ -258,6 +258,13 @@ class _DenoiserTrainFn(torch.autograd.Function):
         return (gz, None, gx, None, *outs)
 
 
+def denoiser_train_supported(p):
+    """Whether the denoiser's training forward / backward (and the noising glue and loss around it) run on libdamc.
+    The training kernels were written and are pinned for nz % 4 == 0 (float4 rows of z, eps and the loss); the toy
+    amortizer's denoiser (nz = 2) trains on its stock layers under autograd."""
+    return p.nz % 4 == 0
+
+
 def denoiser_apply(p, zt, se, xemb):
     """eps_pred = p(zt, logsnr, xemb) given se = SinusoidalPosEmb(logsnr input), differentiable w.r.t. zt,
     xemb and p's parameters (Diffusion_UnetA.forward, diffusion_net.py:477-533)."""

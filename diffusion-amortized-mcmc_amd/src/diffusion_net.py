@@ -258,7 +258,7 @@ class Diffusion_UnetA(nn.Module):
             # time embedding of the per-sample logsnr stays these torch ops, as the reference evaluates it
             from damc import training
 
-            if training.ENABLED:
+            if training.ENABLED and training.denoiser_train_supported(self):
                 return training.denoiser_apply(self, z, self.time_mlp[0](t_in), xemb)
         temb = self.time_mlp(t_in)
         ctx = temb if xemb is None else torch.cat([temb, xemb], dim=1)
@@ -276,27 +276,16 @@ class Diffusion_UnetA(nn.Module):
         return z + out if self.residual else out
 
 
+Diffusion_Unet = Diffusion_UnetA  # the toy tree's name for the same net (toy_example/src/diffusion_net.py:63-139)
+
+
 # ---------------------------------------------------------------------------- amortizer Q
 _ENCODER_FOR = {"cifar10": Encoder_cifar10, "svhn": Encoder_cifar10, "mnist": Encoder_mnist,
                 "celeba64": Encoder_celeba64}
 
 
-class _netQ_U(nn.Module):
-    """Diffusion-based amortizer: encoder + latent-diffusion reverse sweep (diffusion_net.py:537-645)."""
-
-    def __init__(self, nc=3, nz=128, nxemb=128, ntemb=128, nf=4, nif=64, diffusion_residual=False, n_interval=20,
-                 logsnr_min=-20.0, logsnr_max=20.0, var_type="small", with_noise=False, cond_w=0, net_arch="A",
-                 dataset="cifar10"):
-        super().__init__()
-        print("Conditional model Q", with_noise)
-        self.n_interval, self.logsnr_min, self.logsnr_max = n_interval, logsnr_min, logsnr_max
-        self.var_type, self.nz, self.nxemb, self.with_noise = var_type, nz, nxemb, with_noise
-        enc_cls = _ENCODER_FOR.get(dataset, Encoder_celebaHQ)
-        self.encoder = enc_cls(nc=1 if dataset == "mnist" else nc, nemb=nxemb, nif=nif)
-        self.p = Diffusion_UnetA(nz=nz, nxemb=nxemb, ntemb=ntemb, residual=diffusion_residual, nf=nf)
-        self.xemb = nn.Parameter(data=torch.randn(1, self.nxemb), requires_grad=True)
-        self.prior_emb = nn.Sequential(nn.Linear(nz, 128), nn.LeakyReLU(), nn.Linear(128, nxemb))
-        self.cond_w = cond_w
+class _QBase(nn.Module):
+    """What _netQ_U and the toy's _netQ_U_toy share: the reverse sweep on the HIP path and the training loss."""
 
     def forward(self, x=None, b=None, device=None, cond_w=-1):
         """Reverse sweep on the HIP path (damc.amortizer.q_forward)."""
@@ -317,11 +306,14 @@ class _netQ_U(nn.Module):
         return self.prior_emb(noise)
 
     def calculate_loss(self, x=None, z=None, mask=None):
-        """Training loss of the denoiser (diffusion_net.py:624-645).  On ROCm tensors the denoiser's forward and
+        """Training loss of the denoiser (diffusion_net.py:624-645; the toy's is the same lines,
+        toy_example/src/diffusion_net.py:241-263).  On ROCm tensors the denoiser's forward and
         backward run on libdamc (Diffusion_UnetA.forward -> damc.training.denoiser_apply), as do the encoder's
         (_EncoderBase.forward -> damc.training.encoder_apply) and the noising, time embedding and loss
         (damc.training.q_noise_glue / q_loss) and prior_emb (two Linears, used with x None or a mask:
-        damc.training.prior_emb_apply); the random draws stay torch's, in the reference's order."""
+        damc.training.prior_emb_apply); the random draws stay torch's, in the reference's order.  A denoiser the
+        training kernels do not take (damc.training.denoiser_train_supported: the toy's nz = 2) and the toy's MLP
+        encoder run on their stock layers under autograd."""
         assert z is not None
         if x is not None:
             xemb = self.encoder(x)
@@ -333,7 +325,7 @@ class _netQ_U(nn.Module):
         if z.is_cuda and xemb is not None and not z.requires_grad and z.dtype == torch.float32:
             from damc import training
 
-            if training.ENABLED and training.Q_GLUE:
+            if training.ENABLED and training.Q_GLUE and training.denoiser_train_supported(self.p):
                 # the reference's host-generator draw, copied through pinned memory without blocking: a pageable
                 # host-to-device copy waits for the whole stream to drain (tools/h2d_probe.py), which serialised the
                 # host's and the GPU's halves of every Q update
@@ -350,3 +342,40 @@ class _netQ_U(nn.Module):
         eps_pred = self.p(z=fwd["mean"] + fwd["std"] * eps, logsnr=logsnr, xemb=xemb)
         assert eps.shape == eps_pred.shape == (len(z), self.nz)
         return 0.5 * torch.sum((eps - eps_pred) ** 2, dim=1)
+
+
+class _netQ_U(_QBase):
+    """Diffusion-based amortizer: encoder + latent-diffusion reverse sweep (diffusion_net.py:537-645)."""
+
+    def __init__(self, nc=3, nz=128, nxemb=128, ntemb=128, nf=4, nif=64, diffusion_residual=False, n_interval=20,
+                 logsnr_min=-20.0, logsnr_max=20.0, var_type="small", with_noise=False, cond_w=0, net_arch="A",
+                 dataset="cifar10"):
+        super().__init__()
+        print("Conditional model Q", with_noise)
+        self.n_interval, self.logsnr_min, self.logsnr_max = n_interval, logsnr_min, logsnr_max
+        self.var_type, self.nz, self.nxemb, self.with_noise = var_type, nz, nxemb, with_noise
+        enc_cls = _ENCODER_FOR.get(dataset, Encoder_celebaHQ)
+        self.encoder = enc_cls(nc=1 if dataset == "mnist" else nc, nemb=nxemb, nif=nif)
+        self.p = Diffusion_UnetA(nz=nz, nxemb=nxemb, ntemb=ntemb, residual=diffusion_residual, nf=nf)
+        self.xemb = nn.Parameter(data=torch.randn(1, self.nxemb), requires_grad=True)
+        self.prior_emb = nn.Sequential(nn.Linear(nz, 128), nn.LeakyReLU(), nn.Linear(128, nxemb))
+        self.cond_w = cond_w
+
+
+class _netQ_U_toy(_QBase):
+    """The toy example's amortizer (toy_example/src/diffusion_net.py:141-263): an MLP encoder of the 2-d observation,
+    Diffusion_Unet over the 2-d latent, prior_emb.  forward: encoder / prior_emb as one fused MLP launch
+    (damc_mlp_forward), then the row-resident reverse sweep (damc.amortizer.q_forward)."""
+
+    def __init__(self, nz=2, nxemb=128, ntemb=128, nf=4, diffusion_residual=False, n_interval=20, logsnr_min=-20.0,
+                 logsnr_max=20.0, var_type="small", with_noise=False, cond_w=0):
+        super().__init__()
+        print("Conditional model Q", with_noise)
+        self.n_interval, self.logsnr_min, self.logsnr_max = n_interval, logsnr_min, logsnr_max
+        self.var_type, self.nz, self.nxemb, self.with_noise = var_type, nz, nxemb, with_noise
+        self.encoder = nn.Sequential(nn.Linear(2, 128), nn.ReLU(), nn.Linear(128, 128), nn.ReLU(), nn.Linear(128, 128),
+                                     nn.ReLU(), nn.Linear(128, nxemb))
+        self.p = Diffusion_Unet(nz=nz, nxemb=nxemb, ntemb=ntemb, residual=diffusion_residual, nf=nf)
+        self.xemb = nn.Parameter(data=torch.randn(1, self.nxemb), requires_grad=True)
+        self.prior_emb = nn.Sequential(nn.Linear(nz, 128), nn.LeakyReLU(), nn.Linear(128, nxemb))
+        self.cond_w = cond_w

@@ -51,7 +51,7 @@ enum {
   DAMC_LAYER_SMALLC = 3, /* last ConvTranspose2d with Cout <= 4 (to RGB / gray)             */
   DAMC_LAYER_LINEAR = 4  /* nn.Linear (toy MLP generator)                                  */
 };
-enum { DAMC_ACT_NONE = 0, DAMC_ACT_LRELU = 1, DAMC_ACT_TANH = 2, DAMC_ACT_SILU = 3 };
+enum { DAMC_ACT_NONE = 0, DAMC_ACT_LRELU = 1, DAMC_ACT_TANH = 2, DAMC_ACT_SILU = 3, DAMC_ACT_RELU = 4 /* damc_mlp_forward */ };
 /* Convolution engine of a generator layer (every layer of one generator must name the same one):
  *   DAMC_ENGINE_LIMB: layers whose gathered channel count is a multiple of 32 run on the limb engine —
  *     fp32 operands split into 3 bf16 limbs, 6 limb products per fp32 product on bf16 MFMA, fp32
@@ -317,6 +317,26 @@ int damc_encoder_train_backward(const damc_encoder_t* enc, const float* saved, c
 int damc_gemm(const float* a, int lda, const float* b, int ldb, const float* bias, float* c, int ldc, int m,
               int n, int k, int act, float slope, void* stream);
 
+/* A small MLP of nn.Linear layers in ONE launch: the toy amortizer's encoder (workspace/toy_example/src/
+ * diffusion_net.py:166-174, Linear(2,128)-ReLU x3 then Linear(128, nxemb), used at :193 and :245) and its prior_emb
+ * (:180-184, used at :196, :215, :248, :251) at nz = 2.  Weights are the caller's live PyTorch tensors ((out, in),
+ * k contiguous; bias (out) or NULL), read in place: no packing, no workspace.  Each layer applies act in
+ * {DAMC_ACT_NONE, DAMC_ACT_RELU, DAMC_ACT_LRELU(slope)}; layers chain (din of layer i = dout of layer i - 1); every
+ * width is at most DAMC_MLP_MAX_WIDTH.  16 rows per workgroup, activations in LDS; a layer with K % 16 == 0 runs on
+ * the fp32 MFMA, any other K (K = 2) as plain FMAs.  x (batch, layers[0].din), out (batch, last dout). */
+#define DAMC_MLP_MAX_LAYERS 8
+#define DAMC_MLP_MAX_WIDTH 256
+typedef struct {
+  int din, dout, act;
+  float slope;
+  const float *w, *bias;
+} damc_mlp_layer_t;
+typedef struct {
+  int n_layers;
+  damc_mlp_layer_t layers[DAMC_MLP_MAX_LAYERS];
+} damc_mlp_t;
+int damc_mlp_forward(const damc_mlp_t* mlp, const float* x, int batch, float* out, void* stream);
+
 /* Denoiser Diffusion_UnetA (diffusion_net.py:417-533) and its reverse sweep (diffusion_net.py:595-622).
  * Seven ConcatSquashLinearSkipCtx blocks (in0 in1 in2 mid0 out0 out1 out2).  Every weight is the caller's
  * PyTorch tensor in its own layout (nn.Linear (out, in)); the library re-lays them out into its workspace per
@@ -350,6 +370,11 @@ size_t damc_sweep_workspace_bytes(const damc_denoiser_t* d, int batch, int n_ste
  * data-driven hand-offs between the workgroups of a team; at the reference's widths, nf = 4 with nz 128 or 100, a
  * kernel with those shapes compiled in, DAMC_SWEEP_FAST=0 the generic one, bitwise the same); DAMC_SWEEP_TEAM=0
  * runs it as 7 launches per step replayed from a HIP graph cached per (workspace, shapes, schedule).
+ * A denoiser whose nz is no multiple of 4 (the toy's _netQ_U_toy, workspace/toy_example/src/diffusion_net.py:141-239,
+ * nz = 2; any even nz <= 128) runs the chain in its row-resident form instead: one workgroup per 16 rows runs all
+ * steps and blocks for them with the activations in LDS and nothing handed between workgroups (denoiser_rows.hip);
+ * DAMC_SWEEP_ROWS=1 (read per call) takes that form for every shape.  Such a denoiser needs ntemb % 16 == 0,
+ * nxemb % 4 == 0 and a width (in0's dout) that is a multiple of 16 (DAMC_ERR_UNSUPPORTED otherwise).
  *   eps = p(zt, l_t, xemb); pred = c0 * (zt - eps * c1); zt <- last ? pred : c2*zt + c3*pred (+ c4*xi)
  * temb_in (n_steps, ntemb): SinusoidalPosEmb of the step's logsnr input (host, fp32, as the reference);
  * coef (n_steps, 6), a HOST pointer: {sqrt(1+e^-lt), rsqrt(1+e^lt), r*alpha_st, (1-r)*alpha_s, std,
