@@ -8,6 +8,10 @@
 // and the two stacked weight gradients), plus one fused elementwise kernel each way.  The seven ctx
 // Linears (SiLU(cat(temb, xemb)) -> dout_b) run as ONE GEMM over their stacked weights.  ~40 launches
 // forward + ~70 backward for what PyTorch autograd issues as ~1,200.
+//
+// nz is even.  nz % 4 != 0 (the toy amortizer's Diffusion_Unet at nz = 2, workspace/toy_example/src/
+// diffusion_net.py:63-139 as trained by :241-263) pads out2 to the next multiple of 4 inside the workspace and takes
+// the K = nz products off the engine ("nz % 4 != 0" below); for nz % 4 == 0 nothing differs.
 #include <algorithm>
 
 #include "gemm.h"
@@ -279,6 +283,87 @@ __global__ void dz_kernel(const float* __restrict__ g, const float* __restrict__
   dz[i] = v;
 }
 
+// ------------------------------------------------------------------ nz % 4 != 0 (the toy amortizer, nz = 2)
+// The GEMM engines take float4 rows of A (K % 4 == 0, lda % 4 == 0).  With nz even and no multiple of 4, out2 is laid
+// out with dout padded to dp = the next multiple of 4 (zero weight rows / columns and zero biases in the packed
+// workspace, as the sweep's lay_dout does, denoiser.hip), so every stacked width and leading dimension is a multiple
+// of 4 and its padded columns evaluate to exact zeros; the K = nz and K = nz / 2 products around the Fourier embedding
+// are the kernels below.  None of this runs for nz % 4 == 0.
+
+// v = z Bm, X0 = cat(sin(2 pi v), cos(2 pi v), z): input_emb_kernel with the K = nz product inside
+__global__ void input_emb_narrow_kernel(const float* __restrict__ z, const float* __restrict__ bm, int B, int nz,
+                                        float* __restrict__ v, float* __restrict__ X0) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int h = nz / 2, din = 2 * h + nz;
+  if (i >= (long)B * din) return;
+  const int n = (int)(i / din), j = (int)(i - (long)n * din);
+  if (j >= 2 * h) {
+    X0[i] = z[(long)n * nz + j - 2 * h];
+    return;
+  }
+  const int c = j < h ? j : j - h;
+  float p = 0.f;
+  for (int k = 0; k < nz; ++k) p = __builtin_fmaf(z[(long)n * nz + k], bm[k * h + c], p);
+  if (j < h) {
+    v[(long)n * h + c] = p;
+    X0[i] = sinf(kTwoPi * p);
+  } else {
+    X0[i] = cosf(kTwoPi * p);
+  }
+}
+
+// dBm[k][j] = sum_n z[n][k] dv[n][j], z read from X0's last nz columns: one workgroup per entry, the rows strided over
+// its 256 threads and the partials summed by a fixed tree (no atomics)
+__global__ __launch_bounds__(256) void bmat_grad_narrow_kernel(const float* __restrict__ X0, const float* __restrict__ dv,
+                                                               int B, int nz, float* __restrict__ dbm) {
+  __shared__ float red[256];
+  const int h = nz / 2, din = 2 * h + nz;
+  const int k = blockIdx.x / h, j = blockIdx.x - k * h;
+  float acc = 0.f;
+  for (int n = threadIdx.x; n < B; n += 256) acc = __builtin_fmaf(X0[(long)n * din + 2 * h + k], dv[(long)n * h + j], acc);
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) dbm[blockIdx.x] = red[0];
+}
+
+// dzp = dv Bm^T (B x nz), K = nz / 2
+__global__ void dzp_narrow_kernel(const float* __restrict__ dv, const float* __restrict__ bm, int B, int nz,
+                                  float* __restrict__ dzp) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int h = nz / 2;
+  if (i >= (long)B * nz) return;
+  const int n = (int)(i / nz), k = (int)(i - (long)n * nz);
+  float p = 0.f;
+  for (int j = 0; j < h; ++j) p = __builtin_fmaf(dv[(long)n * h + j], bm[k * h + j], p);
+  dzp[i] = p;
+}
+
+// dst (B x dd) = src (B x ds)'s first min(dd, ds) columns (+ z), zeros beyond: eps out of the padded out2 rows
+// (dd = nz < ds = dp; z = zt with residual), and grad_eps into them (dd = dp > ds = nz)
+__global__ void repad_rows_kernel(const float* __restrict__ src, int B, int ds, int dd, const float* __restrict__ z,
+                                  float* __restrict__ dst) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * dd) return;
+  const int n = (int)(i / dd), j = (int)(i - (long)n * dd);
+  float v = j < ds ? src[(long)n * ds + j] : 0.f;
+  if (z) v = z[i] + v;
+  dst[i] = v;
+}
+
+// out2's hyper weight gradients: the (dd x dd) corners of the padded (dp x dp) blocks [gWb; gWg]
+__global__ void hyper_grad_narrow_kernel(const float* __restrict__ gWBG, int dd, int dp, float* __restrict__ gwb,
+                                         float* __restrict__ gwg) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= dd * dd) return;
+  const int o = i / dd, k = i - o * dd;
+  if (gwb) gwb[i] = gWBG[(long)o * dp + k];
+  if (gwg) gwg[i] = gWBG[(long)(dp + o) * dp + k];
+}
+
 inline dim3 grid1(long n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // sum of S split-K slabs [S][M][N] (+ bias[n]) into C (row stride ldc), fixed order
@@ -404,6 +489,10 @@ struct DW {
   float *gWLS[7], *gWBG[7], *gbD[7], *gWC, *gbC, *tmp, *slab;
   int off[8];
   int maxd, maxin;
+  // nz % 4 != 0: out2 laid out lay[6] = dp columns wide (lay[b] = dout elsewhere, and everywhere for nz % 4 == 0)
+  int lay[7];
+  bool narrow;
+  float *epsp, *gpad;  // narrow only: out2's padded output rows, grad_eps padded
 };
 
 int validate(const damc_denoiser_train_t* d) {
@@ -435,14 +524,16 @@ size_t carve(const damc_denoiser_train_t* d, int B, char* base, DW* w) {
   DW t{};
   t.off[0] = 0;
   t.maxd = t.maxin = 0;
+  t.narrow = (nz & 3) != 0;
   for (int b = 0; b < 7; ++b) {
-    t.off[b + 1] = t.off[b] + d->blocks[b].dout;
-    t.maxd = std::max(t.maxd, d->blocks[b].dout);
+    t.lay[b] = (b == 6 && t.narrow) ? (d->blocks[b].dout + 3) & ~3 : d->blocks[b].dout;
+    t.off[b + 1] = t.off[b] + t.lay[b];
+    t.maxd = std::max(t.maxd, t.lay[b]);
     t.maxin = std::max(t.maxin, d->blocks[b].din);
   }
   const int Dt = t.off[7];
   for (int b = 0; b < 7; ++b) {
-    const long di = d->blocks[b].din, dd = d->blocks[b].dout;
+    const long di = d->blocks[b].din, dd = t.lay[b];
     t.WLS_T[b] = take(di * 2 * dd);
     t.WLS[b] = take(2 * dd * di);
     t.WBG_T[b] = take(dd * 2 * dd);
@@ -466,7 +557,7 @@ size_t carve(const damc_denoiser_train_t* d, int B, char* base, DW* w) {
   t.v = take((long)B * h);
   t.zT = take((long)nz * B);
   for (int b = 0; b < 7; ++b) {
-    const long di = d->blocks[b].din, dd = d->blocks[b].dout;
+    const long di = d->blocks[b].din, dd = t.lay[b];
     t.X[b] = take(B * di);
     t.LS[b] = take(B * 2 * dd);
     t.BG[b] = take(B * 2 * dd);
@@ -475,7 +566,7 @@ size_t carve(const damc_denoiser_train_t* d, int B, char* base, DW* w) {
   t.D = take((long)B * 3 * t.maxd);
   t.T = take((long)B * 3 * t.maxd);
   t.dX = take((long)B * t.maxin);
-  for (int b = 0; b < 7; ++b) t.dR[b] = take((long)B * d->blocks[b].dout);
+  for (int b = 0; b < 7; ++b) t.dR[b] = take((long)B * t.lay[b]);
   t.dc = take((long)B * Dt);
   t.du = take((long)B * Dt);
   t.duT = take((long)B * Dt);
@@ -488,7 +579,7 @@ size_t carve(const damc_denoiser_train_t* d, int B, char* base, DW* w) {
   t.dv = take((long)B * h);
   t.dzp = take((long)B * nz);
   for (int b = 0; b < 7; ++b) {
-    const long di = d->blocks[b].din, dd = d->blocks[b].dout;
+    const long di = d->blocks[b].din, dd = t.lay[b];
     t.gWLS[b] = take(2 * dd * di);
     t.gWBG[b] = take(2 * dd * dd);
     t.gbD[b] = take(3 * dd);
@@ -501,6 +592,10 @@ size_t carve(const damc_denoiser_train_t* d, int B, char* base, DW* w) {
   {  // split-K slabs of the (B x N) GEMMs: N <= max(2 dout, din, sum dout, ntemb + nxemb)
     const long nmax = std::max<long>(std::max(2L * t.maxd, (long)t.maxin), std::max<long>(Dt, E));
     t.slab = take((long)kMaxSplit * B * nmax);
+  }
+  if (t.narrow) {  // after everything else: the nz % 4 == 0 carve is unchanged
+    t.epsp = take((long)B * t.lay[6]);
+    t.gpad = take((long)B * t.lay[6]);
   }
   if (w) *w = t;
   return off;
@@ -528,28 +623,33 @@ int forward(const damc_denoiser_train_t* d, const float* zt, const float* se, co
   {  // stack / transpose the live weights (the nets train between calls)
     ProfScope ps("dn_pack", 0.0, s);
     Packer pk(s);
+    const int pad6 = w.lay[6] - d->blocks[6].dout;  // out2's zero columns (nz % 4 != 0 only)
+    if (w.narrow)  // out2's packed weights and biases (one contiguous run of the carve): zero, then the real corners
+      DAMC_CHECK(hipMemsetAsync(w.WLS_T[6], 0, (size_t)((char*)w.WC_T - (char*)w.WLS_T[6]), s));
     for (int b = 0; b < 7; ++b) {
       const damc_csq_block_t& k = d->blocks[b];
-      const int di = k.din, dd = k.dout;
-      pk.add(k.wl, dd, di, w.WLS_T[b], 2 * dd, 0, w.WLS[b], di, 0);
-      pk.add(k.ws, dd, di, w.WLS_T[b], 2 * dd, dd, w.WLS[b], di, dd);
-      pk.add(k.wb, dd, dd, w.WBG_T[b], 2 * dd, 0, w.WBG[b], dd, 0);
-      pk.add(k.wg, dd, dd, w.WBG_T[b], 2 * dd, dd, w.WBG[b], dd, dd);
+      const int di = k.din, dd = k.dout, ld = w.lay[b];  // ld = dd but for the padded out2
+      pk.add(k.wl, dd, di, w.WLS_T[b], 2 * ld, 0, w.WLS[b], di, 0);
+      pk.add(k.ws, dd, di, w.WLS_T[b], 2 * ld, ld, w.WLS[b], di, ld);
+      pk.add(k.wb, dd, dd, w.WBG_T[b], 2 * ld, 0, w.WBG[b], ld, 0);
+      pk.add(k.wg, dd, dd, w.WBG_T[b], 2 * ld, ld, w.WBG[b], ld, ld);
       pk.add(d->wctx[b], dd, E, w.WC_T, Dt, w.off[b], w.WC, E, w.off[b]);
     }
     pk.add(d->tw1, T, T, w.T1_T, T, 0, nullptr, 0, 0);
     pk.add(d->tw2, T, T, w.T2_T, T, 0, nullptr, 0, 0);
-    pk.add(d->bmat, nz, h, w.BmT, nz, 0, nullptr, 0, 0);
+    if (!w.narrow) pk.add(d->bmat, nz, h, w.BmT, nz, 0, nullptr, 0, 0);
+    else pk.add(nullptr, pad6, E, w.WC_T, Dt, w.off[6] + nz, w.WC, E, w.off[6] + nz);  // ctx rows of the zero columns
     pk.flush();
     for (int b = 0; b < 7; ++b) {  // biases as (dout x 1) columns -> stacked rows
       const damc_csq_block_t& k = d->blocks[b];
-      const int dd = k.dout;
+      const int dd = k.dout, ld = w.lay[b];
       pk.add(k.bl, dd, 1, w.bLS[b], 0, 0, nullptr, 0, 0);
-      pk.add(k.bs, dd, 1, w.bLS[b], 0, dd, nullptr, 0, 0);
+      pk.add(k.bs, dd, 1, w.bLS[b], 0, ld, nullptr, 0, 0);
       pk.add(nullptr, dd, 1, w.bBG[b], 0, 0, nullptr, 0, 0);  // _hyper_bias has no bias
-      pk.add(k.bg, dd, 1, w.bBG[b], 0, dd, nullptr, 0, 0);
+      pk.add(k.bg, dd, 1, w.bBG[b], 0, ld, nullptr, 0, 0);
       pk.add(d->bctx[b], dd, 1, w.bC, 0, w.off[b], nullptr, 0, 0);
     }
+    if (w.narrow) pk.add(nullptr, pad6, 1, w.bC, 0, w.off[6] + nz, nullptr, 0, 0);
     pk.flush();
     RC(pk.rc);
   }
@@ -558,7 +658,7 @@ int forward(const damc_denoiser_train_t* d, const float* zt, const float* se, co
   {  // Lt1 and the input embedding's z B are independent: one launch
     Grp gp;
     gp.mm(w.se_in, T, w.T1_T, T, d->tb1, w.a1, T, B, T, T);
-    gp.mm(zt, nz, d->bmat, h, nullptr, w.v, h, B, h, nz);
+    if (!w.narrow) gp.mm(zt, nz, d->bmat, h, nullptr, w.v, h, B, h, nz);  // narrow: inside input_emb_narrow_kernel
     RC(gp.run(w.slab, w.tmp, s));
   }
   hipLaunchKernelGGL(silu_copy_kernel, grid1((long)B * T), dim3(256), 0, s, w.a1, (long)B * T, w.s1);
@@ -577,11 +677,15 @@ int forward(const damc_denoiser_train_t* d, const float* zt, const float* se, co
   for (int b = 0; b < 8; ++b) bo.off[b] = w.off[b];
   hipLaunchKernelGGL(ctx_silu_kernel, grid1((long)B * Dt), dim3(256), 0, s, w.u, B, bo, w.c);
   // input embedding
-  hipLaunchKernelGGL(input_emb_kernel, grid1((long)B * (2 * h + nz)), dim3(256), 0, s, w.v, zt, B, nz, w.X[0], w.zT);
+  if (!w.narrow)
+    hipLaunchKernelGGL(input_emb_kernel, grid1((long)B * (2 * h + nz)), dim3(256), 0, s, w.v, zt, B, nz, w.X[0], w.zT);
+  else
+    hipLaunchKernelGGL(input_emb_narrow_kernel, grid1((long)B * (2 * h + nz)), dim3(256), 0, s, zt, d->bmat, B, nz, w.v,
+                       w.X[0]);
   // blocks; skip inputs: out0 <- in2, out1 <- in1, out2 <- in0
   const int hs_of[7] = {-1, -1, -1, 2, 1, 0, -1};
   for (int b = 0; b < 7; ++b) {
-    const int di = d->blocks[b].din, dd = d->blocks[b].dout;
+    const int di = d->blocks[b].din, dd = w.lay[b];
     const float* cb = w.c + (long)B * w.off[b];
     Grp gp;
     gp.mm(w.X[b], di, w.WLS_T[b], 2 * dd, w.bLS[b], w.LS[b], 2 * dd, B, 2 * dd, di);
@@ -591,8 +695,11 @@ int forward(const damc_denoiser_train_t* d, const float* zt, const float* se, co
     const float* hs = (!last && hs_of[b] >= 0) ? w.R[hs_of[b]] : nullptr;
     hipLaunchKernelGGL(csq_combine_kernel, grid1((long)B * dd), dim3(256), 0, s, w.LS[b], w.BG[b], B, dd, w.R[b],
                        last ? nullptr : w.X[b + 1], last ? 0 : d->blocks[b + 1].din, hs,
-                       (last && d->residual) ? zt : nullptr, last ? eps : nullptr);
+                       (last && d->residual && !w.narrow) ? zt : nullptr, last ? (w.narrow ? w.epsp : eps) : nullptr);
   }
+  if (w.narrow)  // eps = (zt +) the first nz columns of out2's padded rows
+    hipLaunchKernelGGL(repad_rows_kernel, grid1((long)B * nz), dim3(256), 0, s, (const float*)w.epsp, B, w.lay[6], nz,
+                       d->residual ? zt : nullptr, eps);
   return (int)hipGetLastError();
 }
 
@@ -602,9 +709,12 @@ int backward(const damc_denoiser_train_t* d, const float* g, int B, const damc_d
   // block b's input is lrelu(cat(R[pa], R[pc])) (pc < 0: no skip part); b = 0: the input embedding
   const int pa[7] = {-1, 0, 1, 2, 3, 4, 5}, pc[7] = {-1, -1, -1, -1, 2, 1, 0};
   bool seen[7] = {false, false, false, false, false, false, false};  // dR[b] holds a first contribution
+  if (w.narrow)  // grad_eps into out2's padded rows (zeros in the pad columns)
+    hipLaunchKernelGGL(repad_rows_kernel, grid1((long)B * w.lay[6]), dim3(256), 0, s, g, B, nz, w.lay[6],
+                       (const float*)nullptr, w.gpad);
   for (int b = 6; b >= 0; --b) {
-    const int di = d->blocks[b].din, dd = d->blocks[b].dout;
-    const float* dR = b == 6 ? g : w.dR[b];
+    const int di = d->blocks[b].din, dd = w.lay[b];
+    const float* dR = b == 6 ? (w.narrow ? w.gpad : g) : w.dR[b];
     const float* cb = w.c + (long)B * w.off[b];
     hipLaunchKernelGGL(csq_bwd_kernel, grid1((long)B * dd), dim3(256), 0, s, dR, w.LS[b], w.BG[b], B, dd, w.D, w.T);
     {
@@ -618,7 +728,7 @@ int backward(const damc_denoiser_train_t* d, const float* g, int B, const damc_d
     }
     if (b > 0) {
       const int a = pa[b], c = pc[b];
-      const int da = d->blocks[a].dout;
+      const int da = w.lay[a];
       hipLaunchKernelGGL(propagate_kernel, grid1((long)B * di), dim3(256), 0, s, w.dX, B, di, w.R[a], da, w.dR[a],
                          (int)seen[a], c >= 0 ? w.R[c] : nullptr, c >= 0 ? w.dR[c] : nullptr,
                          c >= 0 ? (int)seen[c] : 0);
@@ -628,11 +738,18 @@ int backward(const damc_denoiser_train_t* d, const float* g, int B, const damc_d
   }
   // input embedding (w.dX now holds dX0) -> dBm, dz
   hipLaunchKernelGGL(input_emb_bwd_kernel, grid1((long)B * h), dim3(256), 0, s, w.dX, w.v, B, nz, w.dv);
-  {
+  if (!w.narrow) {
     Grp gp;
     if (gr->bmat) gp.mm(w.zT, B, w.dv, h, nullptr, gr->bmat, h, nz, h, B);
     if (dzt) gp.mm(w.dv, h, w.BmT, nz, nullptr, w.dzp, nz, B, nz, h);
     if (gp.n) RC(gp.run(w.slab, w.tmp, s));
+  } else {  // K = B with nz rows and K = nz / 2: off the engine's float4 rows
+    if (gr->bmat)
+      hipLaunchKernelGGL(bmat_grad_narrow_kernel, dim3((unsigned)(nz * h)), dim3(256), 0, s, (const float*)w.X[0],
+                         (const float*)w.dv, B, nz, gr->bmat);
+    if (dzt)
+      hipLaunchKernelGGL(dzp_narrow_kernel, grid1((long)B * nz), dim3(256), 0, s, (const float*)w.dv, d->bmat, B, nz,
+                         w.dzp);
   }
   if (dzt) {
     hipLaunchKernelGGL(dz_kernel, grid1((long)B * nz), dim3(256), 0, s, d->residual ? g : nullptr, w.dX, w.dzp, B,
@@ -683,14 +800,19 @@ int backward(const damc_denoiser_train_t* d, const float* g, int B, const damc_d
   };
   for (int b = 0; b < 7; ++b) {
     if (ct.n + 9 > kCopyMax) RC(flush());
-    const long di = d->blocks[b].din, dd = d->blocks[b].dout;
+    const long di = d->blocks[b].din, dd = d->blocks[b].dout, ld = w.lay[b];  // the pad rows / columns are dropped
     add(w.gWLS[b], gr->wl[b], dd * di);
-    add(w.gWLS[b] + dd * di, gr->ws[b], dd * di);
-    add(w.gWBG[b], gr->wb[b], dd * dd);
-    add(w.gWBG[b] + dd * dd, gr->wg[b], dd * dd);
+    add(w.gWLS[b] + ld * di, gr->ws[b], dd * di);
+    if (ld == dd) {
+      add(w.gWBG[b], gr->wb[b], dd * dd);
+      add(w.gWBG[b] + dd * dd, gr->wg[b], dd * dd);
+    } else if (gr->wb[b] || gr->wg[b]) {
+      hipLaunchKernelGGL(hyper_grad_narrow_kernel, grid1(dd * dd), dim3(256), 0, s, (const float*)w.gWBG[b], (int)dd,
+                         (int)ld, gr->wb[b], gr->wg[b]);
+    }
     add(w.gbD[b], gr->bl[b], dd);
-    add(w.gbD[b] + dd, gr->bs[b], dd);
-    add(w.gbD[b] + 2 * dd, gr->bg[b], dd);
+    add(w.gbD[b] + ld, gr->bs[b], dd);
+    add(w.gbD[b] + 2 * ld, gr->bg[b], dd);
     add(w.gWC + (long)w.off[b] * E, gr->wctx[b], dd * E);
     add(w.gbC + w.off[b], gr->bctx[b], dd);
   }

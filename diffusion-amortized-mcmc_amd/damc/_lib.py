@@ -128,6 +128,10 @@ class Mlp(ctypes.Structure):  # damc_mlp_t
     _fields_ = [("n_layers", ctypes.c_int), ("layers", MlpLayer * MLP_MAX_LAYERS)]
 
 
+class MlpGrads(ctypes.Structure):  # damc_mlp_grads_t
+    _fields_ = [("w", ctypes.c_void_p * MLP_MAX_LAYERS), ("b", ctypes.c_void_p * MLP_MAX_LAYERS)]
+
+
 class AdamHparams(ctypes.Structure):
     _fields_ = [("neg_step_size", ctypes.c_float), ("one_minus_beta1", ctypes.c_float), ("beta2", ctypes.c_float),
                 ("one_minus_beta2", ctypes.c_float), ("bc2_sqrt", ctypes.c_float), ("eps", ctypes.c_float),
@@ -204,6 +208,10 @@ _SIGS = {
     "damc_q_encoder_fwd": (_I, [ctypes.POINTER(Encoder), _P, _I, _P, _P, _SZ, _P]),
     "damc_gemm": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "damc_mlp_forward": (_I, [ctypes.POINTER(Mlp), _P, _I, _P, _P]),
+    "damc_mlp_train_saved_floats": (_SZ, [ctypes.POINTER(Mlp), _I]),
+    "damc_mlp_train_workspace_bytes": (_SZ, [ctypes.POINTER(Mlp), _I]),
+    "damc_mlp_train_forward": (_I, [ctypes.POINTER(Mlp), _P, _I, _P, _P, _P]),
+    "damc_mlp_train_backward": (_I, [ctypes.POINTER(Mlp), _P, _P, _P, _I, ctypes.POINTER(MlpGrads), _P, _SZ, _P]),
     "damc_conv2d_x3_bytes": (_SZ, [_I, _I, _I]),
     "damc_x3_sign_block": (_I, []),
     "damc_x3_layer_sign_block": (_I, [ctypes.POINTER(Layer), _I]),

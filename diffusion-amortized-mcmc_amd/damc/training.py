@@ -259,10 +259,11 @@ class _DenoiserTrainFn(torch.autograd.Function):
 
 
 def denoiser_train_supported(p):
-    """Whether the denoiser's training forward / backward (and the noising glue and loss around it) run on libdamc.
-    The training kernels were written and are pinned for nz % 4 == 0 (float4 rows of z, eps and the loss); the toy
-    amortizer's denoiser (nz = 2) trains on its stock layers under autograd."""
-    return p.nz % 4 == 0
+    """Whether the denoiser's training forward / backward (and the noising glue and loss around it) run on libdamc:
+    any even nz.  A multiple of 4 runs every Linear on the fp32 GEMM engine; another even nz (the toy amortizer's
+    denoiser, nz = 2) pads out2 to the next multiple of 4 inside the library's workspace and runs the K = nz products
+    around the Fourier embedding as elementwise kernels (denoiser_train.hip)."""
+    return p.nz > 0 and p.nz % 2 == 0
 
 
 def denoiser_apply(p, zt, se, xemb):
@@ -506,6 +507,85 @@ def prior_emb_apply(seq, noise):
     return _PriorEmbTrainFn.apply(noise, d, *params)
 
 
+# ------------------------------------------------------------------------ Q update: a small MLP
+# The toy amortizer's encoder and prior_emb inside calculate_loss (workspace/toy_example/src/diffusion_net.py:166-184,
+# 241-263; six updates per iteration, toy_example.py:209-219) on libdamc (damc_mlp_train_*): the fused forward keeping
+# the hidden activations, and a two-launch backward (dgrad chain, then every layer's dW / db).  No input gradient.
+
+def _mlp_params(seq):
+    """[(layer index, 'w' | 'b', parameter)] of an nn.Sequential's Linears, in module order."""
+    out, n = [], 0
+    for m in seq:
+        if isinstance(m, torch.nn.Linear):
+            out.append((n, "w", m.weight))
+            if m.bias is not None:
+                out.append((n, "b", m.bias))
+            n += 1
+    return out
+
+
+class _MlpTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, desc, sizes, kinds, *params):
+        L = _lib.lib()
+        B = x.shape[0]
+        dev = x.device
+        nsaved, nws = sizes
+        saved = torch.empty(nsaved, dtype=torch.float32, device=dev)
+        out = torch.empty(B, desc.layers[desc.n_layers - 1].dout, dtype=torch.float32, device=dev)
+        check(L.damc_mlp_train_forward(ctypes.byref(desc), ptr(x), B, ptr(saved), ptr(out), _lib.stream_ptr(dev)),
+              "damc_mlp_train_forward")
+        ctx.desc, ctx.nws, ctx.saved_buf, ctx.kinds = desc, nws, saved, kinds
+        ctx.save_for_backward(x, *params)  # autograd's version check: no in-place update before the backward
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x = ctx.saved_tensors[0]
+        params = ctx.saved_tensors[1:]
+        dev = g.device
+        g = g.to(torch.float32).contiguous()
+        outs = _grad_buffers(params, ctx.needs_input_grad[4:])
+        grads = _lib.MlpGrads()
+        for (i, kind), t in zip(ctx.kinds, outs):
+            if t is not None:
+                getattr(grads, kind)[i] = t.data_ptr()
+        ws = _scratch("mlp_bwd", dev, ctx.nws)
+        check(_lib.lib().damc_mlp_train_backward(ctypes.byref(ctx.desc), ptr(x), ptr(ctx.saved_buf), ptr(g), x.shape[0],
+                                                 ctypes.byref(grads), ptr(ws), ctx.nws, _lib.stream_ptr(dev)),
+              "damc_mlp_train_backward")
+        ctx.desc = ctx.saved_buf = None
+        return (None, None, None, None, *outs)
+
+
+def mlp_apply(seq, x):
+    """seq(x) for an nn.Sequential of Linear / ReLU / LeakyReLU on libdamc with grad w.r.t. its parameters (the toy Q
+    update's encoder and prior_emb), or None where the C side does not take the module / input (the caller then runs
+    the stock modules).  x is data or a fresh draw: no gradient flows into it."""
+    from .amortizer import mlp_desc
+
+    if not isinstance(seq, torch.nn.Sequential) or x.dim() != 2 or x.dtype != torch.float32 or x.requires_grad:
+        return None
+    if x.device.type != "cuda":
+        return None
+    entries = _mlp_params(seq)
+    params = [t for _, _, t in entries]
+    if any(p.dtype != torch.float32 or not p.is_contiguous() or p.device != x.device for p in params):
+        return None
+    try:
+        d, _ = mlp_desc(seq, x.device)
+    except NotImplementedError:
+        return None
+    if d.n_layers < 1 or x.shape[1] != d.layers[0].din or x.shape[0] < 1:
+        return None
+    L = _lib.lib()
+    sizes = (int(L.damc_mlp_train_saved_floats(ctypes.byref(d), x.shape[0])),
+             int(L.damc_mlp_train_workspace_bytes(ctypes.byref(d), x.shape[0])))
+    if sizes[0] == 0 or sizes[1] == 0:
+        return None
+    return _MlpTrainFn.apply(x.contiguous(), d, sizes, [(i, k) for i, k, _ in entries], *params)
+
+
 # ------------------------------------------------------------------------------- Q update: encoder
 # Encoder_* (workspace/src/diffusion_net.py:227-413) as trained by Q.calculate_loss: forward on libdamc
 # keeping every conv output, InstanceNorm statistic and layer input; backward through
@@ -561,7 +641,8 @@ def encoder_train_supported(enc, x):
 # per-call scratch of the encoder's training forward / backward (packed weights, conv and InstanceNorm workspaces):
 # kernels are stream-ordered, so one buffer per purpose serves every stage and every call on a stream (round 5: ~20
 # torch.empty calls per Q update, ~0.1 ms of host time)
-_ENC_SCRATCH = {k: _lib.WorkspaceCache() for k in ("w3", "conv", "in", "in_bwd", "conv_bwd", "ebm_bwd", "enc_train", "prior_emb_bwd")}
+_ENC_SCRATCH = {k: _lib.WorkspaceCache() for k in ("w3", "conv", "in", "in_bwd", "conv_bwd", "ebm_bwd", "enc_train", "prior_emb_bwd",
+                                                   "mlp_bwd")}
 
 
 def _scratch(key, device, nbytes):

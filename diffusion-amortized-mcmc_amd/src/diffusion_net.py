@@ -294,16 +294,23 @@ class _QBase(nn.Module):
         return amortizer.q_forward(self, x=x, b=b, device=device, cond_w=cond_w)
 
     def _prior_emb(self, noise):
-        """self.prior_emb(noise): on ROCm with autograd on, libdamc's forward / backward (damc.training.prior_emb_apply),
-        else (or where the C side does not take the shapes) the stock modules."""
+        """self.prior_emb(noise): on ROCm with autograd on, libdamc's forward / backward (damc.training.prior_emb_apply;
+        where that declines -- nz or the batch no multiple of 4, the toy's nz = 2 -- the fused MLP's,
+        damc.training.mlp_apply), else (or where the C side does not take the module) the stock modules."""
         if noise.is_cuda and torch.is_grad_enabled():
             from damc import training
 
             if training.ENABLED:
                 out = training.prior_emb_apply(self.prior_emb, noise)
+                if out is None:
+                    out = training.mlp_apply(self.prior_emb, noise)
                 if out is not None:
                     return out
         return self.prior_emb(noise)
+
+    def _encode_for_loss(self, x):
+        """xemb of calculate_loss: the encoder under autograd (_EncoderBase.forward picks libdamc's training path)."""
+        return self.encoder(x)
 
     def calculate_loss(self, x=None, z=None, mask=None):
         """Training loss of the denoiser (diffusion_net.py:624-645; the toy's is the same lines,
@@ -311,12 +318,13 @@ class _QBase(nn.Module):
         backward run on libdamc (Diffusion_UnetA.forward -> damc.training.denoiser_apply), as do the encoder's
         (_EncoderBase.forward -> damc.training.encoder_apply) and the noising, time embedding and loss
         (damc.training.q_noise_glue / q_loss) and prior_emb (two Linears, used with x None or a mask:
-        damc.training.prior_emb_apply); the random draws stay torch's, in the reference's order.  A denoiser the
-        training kernels do not take (damc.training.denoiser_train_supported: the toy's nz = 2) and the toy's MLP
-        encoder run on their stock layers under autograd."""
+        damc.training.prior_emb_apply); the random draws stay torch's, in the reference's order.  The toy's denoiser
+        (nz = 2) takes the same route, and its MLP encoder and prior_emb the fused MLP's training calls
+        (damc.training.mlp_apply, _netQ_U_toy._encode_for_loss).  A denoiser the training kernels do not take
+        (damc.training.denoiser_train_supported) runs on its stock layers under autograd."""
         assert z is not None
         if x is not None:
-            xemb = self.encoder(x)
+            xemb = self._encode_for_loss(x)
             if mask is not None:
                 xemb = xemb * mask + self._prior_emb(torch.randn(len(x), self.nz, device=x.device)) * (1 - mask)
         else:
@@ -365,7 +373,20 @@ class _netQ_U(_QBase):
 class _netQ_U_toy(_QBase):
     """The toy example's amortizer (toy_example/src/diffusion_net.py:141-263): an MLP encoder of the 2-d observation,
     Diffusion_Unet over the 2-d latent, prior_emb.  forward: encoder / prior_emb as one fused MLP launch
-    (damc_mlp_forward), then the row-resident reverse sweep (damc.amortizer.q_forward)."""
+    (damc_mlp_forward), then the row-resident reverse sweep (damc.amortizer.q_forward).  calculate_loss: encoder and
+    prior_emb on the fused MLP's training calls (damc_mlp_train_*), the denoiser on damc_denoiser_train_*."""
+
+    def _encode_for_loss(self, x):
+        # ROCm with autograd on and x itself not differentiated (data): libdamc's MLP forward + backward
+        # (damc.training.mlp_apply); None where the C side does not take the module or input, then the stock layers
+        if x.is_cuda and torch.is_grad_enabled() and not x.requires_grad:
+            from damc import training
+
+            if training.ENABLED:
+                out = training.mlp_apply(self.encoder, x)
+                if out is not None:
+                    return out
+        return self.encoder(x)
 
     def __init__(self, nz=2, nxemb=128, ntemb=128, nf=4, diffusion_residual=False, n_interval=20, logsnr_min=-20.0,
                  logsnr_max=20.0, var_type="small", with_noise=False, cond_w=0):

@@ -337,6 +337,31 @@ typedef struct {
 } damc_mlp_t;
 int damc_mlp_forward(const damc_mlp_t* mlp, const float* x, int batch, float* out, void* stream);
 
+/* The same MLP under training: the toy amortizer's encoder and prior_emb inside calculate_loss (workspace/toy_example/
+ * src/diffusion_net.py:166-184 as used at :241-263, six times per iteration by toy_example.py:209-219).  The training
+ * calls take what damc_mlp_forward takes with two more conditions: the last layer has DAMC_ACT_NONE, and an LRELU slope
+ * is >= 0 (the backward reads act' from the sign of the saved post-activation).
+ * damc_mlp_train_saved_floats / _workspace_bytes: sizes of `saved` (floats) and of the backward's workspace (bytes) at
+ * this batch; 0 for a descriptor or batch the library does not take. */
+typedef struct {
+  float* w[DAMC_MLP_MAX_LAYERS]; /* dL/dW (out, in) per layer, written (not accumulated); NULL: skipped */
+  float* b[DAMC_MLP_MAX_LAYERS]; /* dL/db (out) per layer; NULL: skipped                                */
+} damc_mlp_grads_t;
+size_t damc_mlp_train_saved_floats(const damc_mlp_t* mlp, int batch);
+size_t damc_mlp_train_workspace_bytes(const damc_mlp_t* mlp, int batch);
+/* Forward of diffusion_net.py:166-184 keeping activations: damc_mlp_forward's kernel (out is bitwise its out), which
+ * also stores every hidden layer's post-activation rows in saved: layer l's (batch, dout_l) block at float offset
+ * batch * (dout_0 + ... + dout_{l-1}), l < n_layers - 1.  One launch. */
+int damc_mlp_train_forward(const damc_mlp_t* mlp, const float* x, int batch, float* saved, float* out, void* stream);
+/* Backward of the same (the encoder's and prior_emb's share of diffusion_net.py:241-263's loss.backward(),
+ * toy_example.py:213): grad_out (batch, last dout) -> every non-NULL grads->w[l], grads->b[l].  No input gradient (x is
+ * data or a fresh draw).  Two launches: a 16-rows-per-workgroup dgrad chain through LDS, and one launch for every
+ * layer's dW and db with the batch walked in a fixed order (no atomics: bitwise reproducible).  Any batch >= 1;
+ * allocates and synchronises nothing. */
+int damc_mlp_train_backward(const damc_mlp_t* mlp, const float* x, const float* saved, const float* grad_out,
+                            int batch, const damc_mlp_grads_t* grads, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 /* Denoiser Diffusion_UnetA (diffusion_net.py:417-533) and its reverse sweep (diffusion_net.py:595-622).
  * Seven ConcatSquashLinearSkipCtx blocks (in0 in1 in2 mid0 out0 out1 out2).  Every weight is the caller's
  * PyTorch tensor in its own layout (nn.Linear (out, in)); the library re-lays them out into its workspace per
@@ -412,7 +437,10 @@ int damc_denoise_step(const damc_denoiser_t* d, const float* xemb, float* zt, in
  * of p, to zt and to xemb (which the caller's autograd carries into the encoder / prior_emb).  All weights
  * in PyTorch layouts (the damc_denoiser_t of the sweep).  temb_in (B, ntemb) is SinusoidalPosEmb of the
  * per-sample logsnr input, evaluated by the caller with the reference's op sequence (diffusion_net.py:447-461,
- * 490-491). */
+ * 490-491).  nz is even.  A multiple of 4 runs every Linear on the fp32 GEMM engine; any other even nz (the toy
+ * amortizer's Diffusion_Unet at nz = 2, workspace/toy_example/src/diffusion_net.py:63-139 as trained by :241-263 and
+ * toy_example.py:209-219) lays out2 out padded to the next multiple of 4 inside the workspace, with zero weights and
+ * biases there, and runs the K = nz products around the Fourier embedding as small kernels of their own. */
 typedef damc_denoiser_t damc_denoiser_train_t;
 typedef struct { /* gradients, same layouts (written, not accumulated; NULL entries are skipped) */
   float* bmat;
