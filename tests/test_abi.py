@@ -58,6 +58,51 @@ def _cifar_desc(ngf=16):
     return g
 
 
+def _svhn_desc(ngf=64):
+    """_netG_svhn topology (diffusion_net.py:53-84): k4 s2 p1 output layer, Cin = 2 ngf."""
+    from damc import _lib
+
+    g = _lib.Generator()
+    g.n_layers, g.nz, g.nc, g.h, g.w = 4, 100, 3, 32, 32
+    spec = [(_lib.LAYER_PROJ, 100, ngf * 8, 4, 1, 0, 1, 4), (_lib.LAYER_UP2, ngf * 8, ngf * 4, 4, 2, 1, 4, 8),
+            (_lib.LAYER_UP2, ngf * 4, ngf * 2, 4, 2, 1, 8, 16), (_lib.LAYER_SMALLC, ngf * 2, 3, 4, 2, 1, 16, 32)]
+    for i, (kind, cin, cout, k, s, p, hin, hout) in enumerate(spec):
+        d = g.layers[i]
+        d.kind, d.cin, d.cout, d.k, d.stride, d.pad = kind, cin, cout, k, s, p
+        d.hin = d.win = hin
+        d.hout = d.wout = hout
+        d.act, d.slope = (_lib.ACT_TANH, 0.0) if i == 3 else (_lib.ACT_LRELU, 0.2)
+    return g
+
+
+RETIRED_SWITCHES = ("DAMC_SMALLC_PROJ_X3", "DAMC_SMALLC_PROJ_GRID", "DAMC_SMALLC_DGRAD_GRID", "DAMC_SMALLC_S2_MFMA",
+                    "DAMC_SMALLC_DGRAD_MFMA", "DAMC_PROJ_SMALL")
+
+
+def test_workspace_size_goes_by_shape_not_environment(monkeypatch):
+    """A workspace carries what its layers can use, by the descriptor and the batch alone: the sign bits the k4 s2
+    output layer's limb-engine dgrad reads (SVHN shape) are sized whatever the retired DAMC_SMALLC_S2_MFMA says."""
+    from damc import _lib
+
+    L = _lib.lib()
+    g = _svhn_desc()
+    monkeypatch.delenv("DAMC_SMALLC_S2_MFMA", raising=False)
+    n = L.damc_posterior_workspace_bytes(ctypes.byref(g), 64)
+    assert n > 0
+    for v in ("0", "1", ""):
+        monkeypatch.setenv("DAMC_SMALLC_S2_MFMA", v)
+        assert L.damc_posterior_workspace_bytes(ctypes.byref(g), 64) == n
+
+
+def test_retired_switches_are_not_in_the_library():
+    from damc import _lib
+
+    blob = open(_lib.LIB_PATH, "rb").read()
+    assert b"DAMC_SMALLC_PROJ16" in blob  # the kept switches are plain strings there
+    for name in RETIRED_SWITCHES:
+        assert name.encode() not in blob, name
+
+
 def test_engine_field_is_validated_host_only():
     """The convolution engine is a per-descriptor field (ABI 2): limb (default) and fp32 descriptors are
     valid and size the same workspace; a generator mixing engines, or naming an unknown one, is refused."""

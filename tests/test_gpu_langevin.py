@@ -374,7 +374,7 @@ def test_split_k_is_bitwise_the_unsplit_kernel(lv, gpu_device, monkeypatch, net,
 
 @pytest.mark.parametrize("net,B", [("cifar10", 5), ("cifar10", 128), ("celeba64", 4)])
 def test_lds_staged_output_projection_is_bitwise_the_direct_kernel(lv, gpu_device, monkeypatch, net, B):
-    """The output layer's projection stage staged through LDS (generator.hip smallc_proj_lds_kernel: same MFMA
+    """The output layer's projection stage staged through LDS (smallc.hip smallc_proj_lds_kernel: same MFMA
     sequence, operands from LDS) gives the same bits as the direct-load kernel: 2 posterior steps at full width
     (CIFAR k3: one 32-column tile, ragged last wave at B=5; CelebA-64 k4 s2: two tiles) with
     DAMC_SMALLC_PROJ_LDS=0 vs 1 (with the round-4 proj16 kernel and the fused projection switched off, so these two
@@ -487,7 +487,7 @@ def test_skinny_first_layer_is_bitwise(lv, gpu_device, monkeypatch, B):
 @pytest.mark.parametrize("net,B", [("cifar10", 100), ("cifar10", 128), ("celeba64", 32)])
 def test_lds_staged_gather_is_bitwise_the_direct_gather(lv, gpu_device, monkeypatch, net, B):
     """The output layer's gather (delta, x_hat from the per-tap projections and their 128-channel partials)
-    staged through LDS (generator.hip smallc_gather_lds_kernel for k3 s1 row strips, smallc_gather_s2_lds_kernel for
+    staged through LDS (smallc.hip smallc_gather_lds_kernel for k3 s1 row strips, smallc_gather_s2_lds_kernel for
     k4 s2 16 x 32 tiles): 2 noisy posterior steps bitwise equal to the direct per-pixel gather
     (DAMC_SMALLC_GATHER_LDS=0), at batches whose tiles fill the chip (the LDS forms run from 256 workgroups)."""
     from damc import synth
