@@ -1051,8 +1051,11 @@ constexpr int X3_NARROW = 4194304;
 // stride-2 4 x 4 conv) read the same 256 input pixels displaced by 0 / +-1 grid positions, so the undisplaced 256 x
 // 128-B fp32 image is staged once per group (8 KB instead of 32 KB of A per K tile) and, since round 9, split into its
 // limbs once, into an LDS limb image; each tap's fragment reads take limb-image row r + delta(tap), or an all-zero row
-// where the tap falls in the padding: the same limbs of the same fp32 operands, bitwise the per-tap staging.  (Rounds
-// 7-8 under this value: the taps read the fp32 image and each ran the split in registers.)
+// where the tap falls in the padding: the same limbs of the same fp32 operands, bitwise the per-tap staging.  Since
+// round 11 the loop runs on the 4 (M) x 2 (N) wave grid of the limb-A base loop: no wave splits anything in registers
+// any more, and a B fragment feeds four A tiles instead of two (24 instead of 30 ds_read_b128 per wave and K tile).
+// (Rounds 7-8 under this value: the taps read the fp32 image and each ran the split in registers; rounds 9-10: the
+// limb image on the per-tap loop's 8 x 1 waves.)
 constexpr int X3_TAPSHARE = 16777216;
 __device__ __forceinline__ int f32a_swz(int r) { return ((r >> 1) & 7) ^ ((((r >> 2) ^ (r >> 3)) & 1) << 1); }
 // the swizzle of the X3_TAPSHARE fp32 staging image.  Chosen in round 7, when the taps read it at rows r + delta: the
@@ -1065,6 +1068,8 @@ static_assert(X3_NEGK % 32 == 0 && (X3_NEGK & (X3_NEGK - 1)) == 0, "sign blocks 
 constexpr int X3_CHUNKS = 12;  // 16-B chunks per row and K tile (4 octets x 3 limbs)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+template <int N>
+using x3_ic = std::integral_constant<int, N>;
 
 // V, gemm_x3_kernel's variant bits.  The value is part of the kernel's name, which committed profiles and the tools
 // match on, so the bits keep their values.  (The retired experiment bits and what they measured: DESIGN.md.)
@@ -1173,7 +1178,8 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   constexpr int BM = WIDE ? 128 : NARROW ? 64 : X3_BM, BN = WIDE ? 256 : X3_BN;
   // X3_F32A: A staged as fp32 (4 B per element instead of 6 B of limbs) and split into its RNE limbs in registers after
   // the fragment read, the same split as the producing epilogue's, so the MFMA operands and results are bitwise the
-  // limb path's; waves 8 along M x 1 along N (each 32 x 128), so every A element is split by one wave only
+  // limb path's; waves 8 along M x 1 along N (each 32 x 128), so every A element is split by one wave only (the per-tap
+  // loop; the X3_TAPSHARE loop reads its A fragments as limbs from LDS and keeps the 4 x 2 grid of 64 x 64)
   constexpr bool F32A = (V & X3_F32A) != 0;
   static_assert(!F32A || (OM != O_WGRAD && !WIDE), "F32A: 256 x 128 tiles, not the weight gradient");
   constexpr int AROWB = F32A ? X3A_ROWB : X3_ROWB, ESZ = F32A ? 4 : 6;
@@ -1495,8 +1501,11 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     };
     // B image buf: at BOFF behind the start of buffer buf
     constexpr int BOFF = TSHARE ? TS_B : BM * X3A_ROWB, BBUF = TSHARE ? BN * X3_ROWB : BUFB;
+    // the tap-shared loop keeps the wave's LDS-DMA base in an SGPR: no v_readfirstlane per DMA instruction (round 11:
+    // they pay for the two more read-address v_xor of the 4 x 2 grid, SQ_INSTS_VALU stays below round 9's)
+    const int wbase_s = TSHARE ? __builtin_amdgcn_readfirstlane(wbase) : 0;
     auto dma_b = [&](int k0, int buf) {
-      unsigned char* dst = smem + buf * BBUF + BOFF + wbase;
+      unsigned char* dst = smem + buf * BBUF + BOFF + (TSHARE ? wbase_s : wbase);
 #pragma unroll
       for (int j = 0; j < BJ; ++j)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_t)(dst + 512 * 16 * j), 16, (int)boff[j], k0 * 6, 0, 0);
@@ -1549,14 +1558,14 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     // its residue, so it takes that row's slot and the lane group stays conflict-free.
     // TS_TOFF, the read table: for walk position pos and tile row r, the LDS byte of limb 0, octet 0 ^ x3_swz of the
     // row tap(pos) reads for r -- image row r + delta(pos), or the zero row -- built once per workgroup, so a tile's
-    // read addresses cost two ds_read_b32 and two v_xor per lane.
+    // read addresses (four rows 16 apart per lane) cost two ds_read2_b32 and four v_xor per lane.
     // Timeline of group G (K tiles 4 G .. 4 G + 3): the pieces of image G + 1 are DMA'd during tiles 4 G .. 4 G + 2 into
     // the staging image (its last reader, the conversion of G during tile 4 G - 1, retired by that tile's barrier);
-    // during tile 4 G + 3 every thread reads its 16 staged values (the two octets it would read as fragments), splits
-    // them in that tile's MFMA gaps and writes the 6 limb octets over image G, whose last fragment reads (A(4 G + 3), one
-    // tile ahead) were in tile 4 G + 2; the barrier of 4 G + 3 publishes image G + 1.  Tile 4 G + 4 reads its own
-    // fragments at its start, as B's are read, and A(4 G + 5) during its MFMAs; sign blocks are whole groups
-    // (x3_tapshare_shape), so only a group's last tile flushes.
+    // during tile 4 G + 3 every thread reads its 16 staged values (two octets, rows wave * 32 + 16 a + lrow), splits
+    // them in that tile's MFMA gaps and writes the 6 limb octets over image G, behind the tile's second barrier: every
+    // tile reads its own A fragments (the 4 x 2 grid's twelve do not fit the register file a tile ahead), so tile
+    // 4 G + 3 still reads image G in its first column; the barrier of 4 G + 3 publishes image G + 1.  Sign blocks are
+    // whole groups (x3_tapshare_shape), so only a group's last tile flushes.
     unsigned ts_ibase = 0;
     int ts_nv = 0, ts_pstr = 0;
     if constexpr (TSHARE) {
@@ -1597,29 +1606,24 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         sl = gg >> 2;
         coff = ((1 - (c >> 1)) * Win + (1 - (c & 1))) * Cg * 4;
       }
-      unsigned char* dst = smem + TS_STG + wbase + 512 * 16 * j;
+      unsigned char* dst = smem + TS_STG + wbase_s + 512 * 16 * j;
       const int vo = j < ts_nv ? (int)(ts_ibase + (unsigned)(j * ts_pstr)) : (int)KM_OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_t)dst, 16, vo, sl * (X3_BK * 4) + coff, 0, 0);
     };
-    // the LDS byte addresses (limb 0; limb l is 64 l further) of this lane's two fragment rows of local K tile ktn, from
-    // the table; every address is an image row or a zero row
-    const int ts_tb = TS_TOFF + (wave * 32 + lrow) * 4;
-    auto ts_addr = [&](int ktn, int (&o)[2]) {
+    // the LDS byte addresses (limb 0; limb l is 64 l further) of this lane's four fragment rows (A tile i of the wave's
+    // 64 rows: row 64 wm + 16 i + lrow) of local K tile ktn, from the table: four words 64 B apart, two ds_read2_b32;
+    // every address is an image row or a zero row
+    const int ts_tb = TS_TOFF + (wm * 64 + lrow) * 4;
+    auto ts_addr = [&](int ktn, int (&o)[4]) {
       const int ta = ts_tb + ((kt0 + ktn) & (TS_NT - 1)) * (BM * 4);
 #pragma unroll
-      for (int a = 0; a < 2; ++a) o[a] = *reinterpret_cast<const int*>(smem + ta + a * 64) ^ (loct << 4);
-    };
-    auto rd_limb = [&](const int (&o)[2], bf16x8 (&f)[2][3], int a, int l) {
-      f[a][l] = *reinterpret_cast<const bf16x8*>(smem + o[a] + l * 64);
+      for (int i = 0; i < 4; ++i) o[i] = *reinterpret_cast<const int*>(smem + ta + i * 64) ^ (loct << 4);
     };
     // the conversion: this lane's two octets (rows wave * 32 + 16 a + lrow, octet loct) of the staging image ...
     const int cv_rd = TS_STG + (wave * 32 + lrow) * X3A_ROWB + ((2 * loct) ^ ts_swz(lrow)) * 16;
-    auto rd_stg = [&](f32x4 (&av)[2][2]) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        av[a][0] = *reinterpret_cast<const f32x4*>(smem + cv_rd + a * 16 * X3A_ROWB);
-        av[a][1] = *reinterpret_cast<const f32x4*>(smem + (cv_rd ^ 16) + a * 16 * X3A_ROWB);
-      }
+    auto rd_stg = [&](f32x4 (&av)[2][2], int a) {
+      av[a][0] = *reinterpret_cast<const f32x4*>(smem + cv_rd + a * 16 * X3A_ROWB);
+      av[a][1] = *reinterpret_cast<const f32x4*>(smem + (cv_rd ^ 16) + a * 16 * X3A_ROWB);
     };
     // ... and their limbs into the limb image
     const int cv_wr = (wave * 32 + lrow) * X3_ROWB + (loct ^ sw) * 16;
@@ -1653,6 +1657,22 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
             (void*)(p.kslab + ((long)zph * p.ksplit + zsl * p.kbpw) * ntile * (BM * BN)), (short)0,
             p.kbpw * ntile * (BM * BN) * 4, 0x00020000);
         const int soff = ((kt >> FLOG) * ntile + tm * ntn + tn) * (BM * BN * 4);
+        if constexpr (TSHARE) {
+          // the tap-shared loop runs on the 4 x 2 grid itself (round 11): acc16[i][j] is tile i * 4 + j of wave `wave`;
+          // the offset whole in the VGPR and soffset 0, as below
+          const int voff = (wave * 1024 + lane) * 16;
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              acc16[i][j] *= sg;
+              if (m0 + wm * 64 + i * 16 < p.M)
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc16[i][j]), rsl,
+                                                       voff + soff + (i * 4 + j) * 1024, 0, 0);
+              acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+          return;
+        }
         const int voff = ((wave >> 1) * 2 * 1024 + ((wave & 1) * 2) * 4 * 64 + lane) * 16;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -1679,7 +1699,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
       }
     };
     if constexpr (TSHARE) {
-      int oa[2], ob[2];  // fragment read addresses, two K tiles in flight
+      int oa[4], ob[4];  // fragment read addresses: this K tile's and the next one's
       if (nk > 0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) dma_img(0, j);
@@ -1688,82 +1708,169 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
       __syncthreads();  // the table, the zero rows, the staged image 0, B(0)
       {
         f32x4 av0[2][2];
-        rd_stg(av0);
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
+          rd_stg(av0, a);
 #pragma unroll
           for (int e = 0; e < 8; e += 2) split2(av0, fx, a, e);
           wr_limb(fx, a);
         }
       }
       ts_addr(0, oa);
-      ts_addr(1, ob);
       __syncthreads();  // limb image 0
-      // K tile kt = position PH of its group; fc: its A limbs (PH 0 reads them first), fn: A(kt + 1)'s, read through
-      // on (PH 0-2), or the conversion's (PH 3); of: receives A(kt + 2)'s addresses (PH 0 reads its own through it first)
-      auto tile = [&](int kt, auto PH_, bf16x8 (&fc)[2][3], bf16x8 (&fn)[2][3], int (&on)[2], int (&of)[2]) {
+      // K tile kt = position PH of its group, on the 4 x 2 wave grid (round 11): acc16[i][j] is A tile i (image rows
+      // 64 wm + 16 i + lrow through the read table) x B tile j (B image rows 64 wn + 16 j + lrow), so a B fragment feeds
+      // four A tiles: 12 A + 12 B ds_read_b128 per wave and tile instead of 6 + 24.  The four A tiles stay resident and
+      // B streams through two slots, column by column -- (0, j) .. (3, j) for j = 0 .. 3 --: A tiles 1 .. 3 are read one
+      // group of MFMAs ahead of their first use (every A read of the tile is issued within its first 12 MFMAs), B tile
+      // j + 1 twelve MFMAs ahead.  A tile 0 of tiles PH 1 .. 3 is read during the previous tile's last 12 MFMAs, across its
+      // barrier (the image does not change inside a group), so only B tile 0 stands in front of their first MFMA; PH 0
+      // reads its own (six reads in front).  Measured: +0.2-0.3 % over reading every tile's own A tile 0
+      // (profiles/r11/wave_grid_ab.txt).  oc: this tile's read addresses; on receives A(kt + 1)'s.
+      // PH 3 converts image G + 1 over image G, which this tile's own A fragments still come from: a second barrier
+      // after column 0 (every wave's A fragments in registers) stands between them and the first limb write.  That
+      // barrier waits for the LDS-DMA in flight as any barrier does, so PH 3 issues B(kt + 1) behind it (in front of it:
+      // 3 % slower).  The split runs one 16-row half at a time, in the MFMA gaps of column 1 and of column 2 (8 staged
+      // values and 12 limb registers live at once; the whole conversion at once spills).
+      bf16x8 pa[3];  // A tile 0 of the next K tile, read during this one's last MFMAs
+      auto tile = [&](int kt, auto PH_, int (&oc)[4], int (&on)[4]) {
         constexpr int PH = decltype(PH_)::value;
+        constexpr bool PFI = PH > 0, PFO = PH < 3;  // A tile 0 arrives in pa / the next tile's is read into it
         const unsigned char* base = smem + (PH & 1) * BBUF;  // groups start at even local tiles
-        if (kt + 1 < nk) dma_b(kbeg + (kt + 1) * X3_BK, (PH + 1) & 1);
-        if constexpr (PH < 3) {  // the next group's image: pieces 0 and 1, 2, 3
-          const int G = (kt >> 2) + 1;
+        if constexpr (PH < 3) {
+          if (kt + 1 < nk) dma_b(kbeg + (kt + 1) * X3_BK, (PH + 1) & 1);
+          const int G = (kt >> 2) + 1;  // the next group's image: pieces 0 and 1, 2, 3
           if (4 * G < nk) {
             if constexpr (PH == 0) dma_img(G, 0);
             dma_img(G, PH + 1);
           }
         }
-        auto rd_b = [&](int t, int slot) {
-#pragma unroll
-          for (int l = 0; l < 3; ++l) fb[slot][l] = *reinterpret_cast<const bf16x8*>(base + brow + t * 16 * X3_ROWB + l * 16);
-        };
+        bf16x8 fa[4][3], fq[2][3], fl[2][3];
         f32x4 av[2][2];
-        if constexpr (PH == 0) {
+        auto rd_a = [&](int i) {
 #pragma unroll
-          for (int i = 0; i < 6; ++i) rd_limb(of, fc, i / 3, i % 3);
-        }
-        // (past the last group the conversion reads a stale, in-bounds staging image into an image nobody reads)
-        if constexpr (PH == 3) rd_stg(av);
-        rd_b(0, 0);
-        rd_b(1, 1);
+          for (int l = 0; l < 3; ++l) fa[i][l] = *reinterpret_cast<const bf16x8*>(smem + oc[i] + l * 64);
+        };
+        auto rd_b = [&](int j) {
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          if constexpr (PH == 3) split2(av, fn, t >> 2, (t & 3) * 2);
-          mfma6(fc, t);
-          if (t + 2 < 8) rd_b(t + 2, t & 1);
-          if constexpr (PH < 3) {
-            if (t < 6) rd_limb(on, fn, t / 3, t % 3);
-          }
-          if (t == 0) ts_addr(kt + 2, of);
-          if constexpr (PH == 3) {
-            if (t == 4) wr_limb(fn, 0);
-            if (t == 7) wr_limb(fn, 1);
-          }
-        }
-        // schedule: this tile's own A reads (PH 0) or the staged values (PH 3) and B tiles 0 and 1 first, then per B tile
-        // t its 12 MFMAs (PH 3: the split's VALU in their gaps), then the reads and writes written behind them above
-        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, PH == 0 ? 12 : PH == 3 ? 10 : 6, 0);
+          for (int l = 0; l < 3; ++l)
+            fq[j & 1][l] = *reinterpret_cast<const bf16x8*>(base + brow + (wn * 64 + j * 16) * X3_ROWB + l * 16);
+        };
+        auto mf = [&](int i, int j) {  // the six limb products of A tile i x B tile j, smallest first
+          const int sl = j & 1;
+          f32x4 c = acc16[i][j];
+          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][2], fq[sl][0], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fq[sl][1], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fq[sl][2], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fq[sl][0], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fq[sl][1], c, 0, 0, 0);
+          acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fq[sl][0], c, 0, 0, 0);
+        };
+        // N MFMAs of the schedule, V of the split's VALU behind each (PH 3)
+        auto pin = [&](auto N_, auto V_) {
 #pragma unroll
-        for (int t = 0; t < 8; ++t) {
-#pragma unroll
-          for (int m = 0; m < 12; ++m) {
+          for (int m = 0; m < decltype(N_)::value; ++m) {
             __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
-            if constexpr (PH == 3) __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
+            if constexpr (decltype(V_)::value > 0) __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
+            if constexpr (decltype(V_)::value > 1) __builtin_amdgcn_sched_group_barrier(SG_VALU, 1, 0);
           }
-          if (t + 2 < 8) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
-          if (PH < 3 && t < 6) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 1, 0);
-          if (t == 0) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 2, 0);  // the two table reads
-          if (PH == 3 && (t == 4 || t == 7)) __builtin_amdgcn_sched_group_barrier(SG_DS_WR, 3, 0);
+        };
+        constexpr x3_ic<0> V0{};
+        constexpr x3_ic<PH == 3 ? 2 : 0> V2{};
+        // column 0, with the tile's remaining A reads, then B tile 1 and the next tile's addresses, behind its MFMAs
+        if constexpr (PFI) {
+#pragma unroll
+          for (int l = 0; l < 3; ++l) fa[0][l] = pa[l];
+        } else {
+          rd_a(0);
         }
+        rd_b(0);
+        rd_a(1);
+        mf(0, 0);
+        rd_a(2);
+        mf(1, 0);
+        rd_a(3);
+        mf(2, 0);
+        rd_b(1);
+        ts_addr(kt + 1, on);
+        // (past the last group the conversion reads a stale, in-bounds staging image into an image nobody reads)
+        if constexpr (PH == 3) rd_stg(av, 0);
+        mf(3, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, PFI ? 3 : 6, 0);
+        pin(x3_ic<1>{}, V0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+        pin(x3_ic<5>{}, V0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+        pin(x3_ic<6>{}, V0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+        pin(x3_ic<6>{}, V0);
+        // B tile 1, the table's two ds_read2_b32, PH 3: the staged values of the conversion's first half
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, PH == 3 ? 3 + 2 + 2 : 3 + 2, 0);
+        pin(x3_ic<6>{}, V0);
+        if constexpr (PH == 3) {
+          // every A fragment of this wave is in its registers; behind the barrier, every wave's
+          __builtin_amdgcn_sched_barrier(0);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+          __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+          __builtin_amdgcn_sched_barrier(0);
+          if (kt + 1 < nk) dma_b(kbeg + (kt + 1) * X3_BK, 0);
+        }
+        // columns 1 .. 3: B tile j + 1 into the slot column j - 1 released, 12 MFMAs ahead; PH 3: one half of the
+        // conversion in the gaps of column 1, the other in those of column 2, each written at the next column's start
+        if constexpr (PH == 3) split2(av, fl, 0, 0);
+        mf(0, 1);
+        if constexpr (PH == 3) split2(av, fl, 0, 2);
+        mf(1, 1);
+        rd_b(2);
+        if constexpr (PH == 3) split2(av, fl, 0, 4);
+        mf(2, 1);
+        if constexpr (PH == 3) split2(av, fl, 0, 6);
+        mf(3, 1);
+        if constexpr (PH == 3) {
+          wr_limb(fl, 0);
+          rd_stg(av, 1);
+          split2(av, fl, 1, 0);
+        }
+        mf(0, 2);
+        if constexpr (PH == 3) split2(av, fl, 1, 2);
+        mf(1, 2);
+        rd_b(3);
+        if constexpr (PH == 3) split2(av, fl, 1, 4);
+        mf(2, 2);
+        if constexpr (PH == 3) split2(av, fl, 1, 6);
+        mf(3, 2);
+        if constexpr (PH == 3) wr_limb(fl, 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mf(i, 3);
+        if constexpr (PFO) {
+#pragma unroll
+          for (int l = 0; l < 3; ++l) pa[l] = *reinterpret_cast<const bf16x8*>(smem + on[0] + l * 64);
+        }
+        pin(x3_ic<12>{}, V2);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+        pin(x3_ic<12>{}, V2);
+        if constexpr (PH == 3) {
+          __builtin_amdgcn_sched_group_barrier(SG_DS_WR, 3, 0);
+          __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 2, 0);
+        }
+        pin(x3_ic<12>{}, V2);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+        pin(x3_ic<12>{}, V2);
+        if constexpr (PH == 3) __builtin_amdgcn_sched_group_barrier(SG_DS_WR, 3, 0);
+        pin(x3_ic<12>{}, V0);
+        if constexpr (PFO) __builtin_amdgcn_sched_group_barrier(SG_DS_RD, 3, 0);
+        pin(x3_ic<12>{}, V0);
         __syncthreads();
         if constexpr (PH == 3) {
           if (((kt + 1) & (FLUSH - 1)) == 0) flush_blk(kt);
         }
       };
-      for (int kt = 0; kt < nk; kt += 4) {  // one group per trip: the limb sets and address pairs trade roles in place
-        tile(kt, std::integral_constant<int, 0>{}, fx, fy, ob, oa);
-        tile(kt + 1, std::integral_constant<int, 1>{}, fy, fx, oa, ob);
-        tile(kt + 2, std::integral_constant<int, 2>{}, fx, fy, ob, oa);
-        tile(kt + 3, std::integral_constant<int, 3>{}, fy, fx, ob, ob);
+      for (int kt = 0; kt < nk; kt += 4) {  // one group per trip: the address sets trade roles in place
+        tile(kt, std::integral_constant<int, 0>{}, oa, ob);
+        tile(kt + 1, std::integral_constant<int, 1>{}, ob, oa);
+        tile(kt + 2, std::integral_constant<int, 2>{}, oa, ob);
+        tile(kt + 3, std::integral_constant<int, 3>{}, ob, oa);
       }
     } else {
       if (nk > 0) {
@@ -2021,9 +2128,12 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         auto store = [&](auto NT_) {
           constexpr int NT = decltype(NT_)::value;
           constexpr int RG = F32A ? 2 : 1;
+          // the tap-shared K loop has no register to carry this wave's row base across it: taken from the thread id anew
+          int ptid = tid;
+          if constexpr (TSHARE) asm volatile("" : "+v"(ptid));
 #pragma unroll
           for (int g = 0; g < RG; ++g) {
-            const int r0 = F32A ? wave * 32 + g * 16 : wave * 16;
+            const int r0 = F32A ? (TSHARE ? ptid >> 6 : wave) * 32 + g * 16 : wave * 16;
             // one row group at a time: scheduled across this point, the F32A ConvT forward (CIFAR B=128) measured
             // 0.8 % slower
             __builtin_amdgcn_sched_barrier(0);
@@ -2051,7 +2161,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     }
   };
   if (tid < BM) rowtab[tid] = (m0 + tid < p.M) ? gemm_row_offset<OM>(p, m0 + tid, py, px) : -1L;
-  if (F32A) {
+  if (F32A && !TSHARE) {  // the per-tap loop's 8 x 1 waves; the tap-shared loop's 4 x 2 grid takes the last branch
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
