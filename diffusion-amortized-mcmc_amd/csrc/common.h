@@ -81,6 +81,9 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t chain, ui
 }
 
 enum { DAMC_STREAM_POSTERIOR = 0x51, DAMC_STREAM_PRIOR = 0x52, DAMC_STREAM_SWEEP = 0x53 };
+// the guided sweep's per-step prior-embedding noise, keyed (seed, chain_base + row, step k, quad): drawn by the caller
+// (damc_philox_normal), never by a kernel
+enum { DAMC_STREAM_GUIDE = 0x54 };
 
 // element i & 3 of a 4-value draw without a runtime-indexed private array (which the compiler would place in
 // scratch memory: a per-dispatch scratch setup and slow private loads for every kernel that draws noise)

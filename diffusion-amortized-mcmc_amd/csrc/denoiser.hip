@@ -1447,28 +1447,31 @@ __global__ void silu_kernel(const float* x, long n, float* y) {
   }
 }
 
-// c[k][b][s] = SiLU(px[b][s] + qt[k][s])
-__global__ void ctx_kernel(const float* __restrict__ px, const float* __restrict__ qt, int B, int S, long total,
-                           float* __restrict__ c) {
+// c[k][b][s] = SiLU(px[k * pxstep + b * S + s] + qt[k][s]): pxstep 0 for the one px of a sweep's xemb, B S for a px
+// per step (the guided sweep's unconditional embeddings)
+__global__ void ctx_kernel(const float* __restrict__ px, long pxstep, const float* __restrict__ qt, int B, int S,
+                           long total, float* __restrict__ c) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const long per = (long)B * S;
   const long k = i / per;
   const long r = i - k * per;
   const int s = (int)(r % S);
-  const float u = px[r] + qt[k * S + s];
+  const float u = px[k * pxstep + r] + qt[k * S + s];
   c[i] = u / (1.f + expf(-u));
 }
 
 // the same, 4 columns per thread (S % 4 == 0), grid.y = step: no 64-bit division per element, and SiLU on the
 // transcendental unit (exp2 and reciprocal, ~1 ulp each) unless exact (DAMC_SWEEP_HYPER_SIGMOID=exact: ctx_kernel's
 // expf and IEEE division); 16 M SiLUs per CIFAR sweep
-__global__ __launch_bounds__(256) void ctx4_kernel(const float* __restrict__ px, const float* __restrict__ qt, int BS,
-                                                   int S, int exact, float* __restrict__ c) {
+__global__ __launch_bounds__(256) void ctx4_kernel(const float* __restrict__ px, long pxstep,
+                                                   const float* __restrict__ qt, int BS, int S, int exact,
+                                                   float* __restrict__ c) {
   const int r4 = 4 * (blockIdx.x * 256 + threadIdx.x), k = blockIdx.y;
   if (r4 >= BS) return;
   const int s = r4 % S;
-  const f32x4 a = *reinterpret_cast<const f32x4*>(px + r4), b = *reinterpret_cast<const f32x4*>(qt + (long)k * S + s);
+  const f32x4 a = *reinterpret_cast<const f32x4*>(px + k * pxstep + r4),
+              b = *reinterpret_cast<const f32x4*>(qt + (long)k * S + s);
   f32x4 o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -1479,16 +1482,17 @@ __global__ __launch_bounds__(256) void ctx4_kernel(const float* __restrict__ px,
 }
 
 // the ctx launch of a sweep: ctx4_kernel where the rows allow float4 access
-int launch_ctx(const float* px, const float* qt, int n, int B, int S, float* cx, hipStream_t s) {
+int launch_ctx(const float* px, long pxstep, const float* qt, int n, int B, int S, float* cx, hipStream_t s) {
   const char* hs = getenv("DAMC_SWEEP_HYPER_SIGMOID");  // (read per call)
   const int exact = hs && strcmp(hs, "exact") == 0;
   const long BS = (long)B * S;
-  if (S % 4 == 0 && BS < (1L << 31) && (uintptr_t)px % 16 == 0 && (uintptr_t)qt % 16 == 0 && (uintptr_t)cx % 16 == 0) {
-    hipLaunchKernelGGL(ctx4_kernel, dim3((unsigned)((BS / 4 + 255) / 256), (unsigned)n), dim3(256), 0, s, px, qt,
-                       (int)BS, S, exact, cx);
+  if (S % 4 == 0 && pxstep % 4 == 0 && BS < (1L << 31) && (uintptr_t)px % 16 == 0 && (uintptr_t)qt % 16 == 0 && (uintptr_t)cx % 16 == 0) {
+    hipLaunchKernelGGL(ctx4_kernel, dim3((unsigned)((BS / 4 + 255) / 256), (unsigned)n), dim3(256), 0, s, px, pxstep,
+                       qt, (int)BS, S, exact, cx);
   } else {
     const long tot = (long)n * BS;
-    hipLaunchKernelGGL(ctx_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, px, qt, B, S, tot, cx);
+    hipLaunchKernelGGL(ctx_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, px, pxstep, qt, B, S,
+                       tot, cx);
   }
   return (int)hipGetLastError();
 }
@@ -2319,86 +2323,98 @@ extern "C" size_t damc_sweep_workspace_bytes(const damc_denoiser_t* d, int B, in
   return carve(d, B, n, nullptr, nullptr);
 }
 
-// step_offset: Philox step index of the first noisy step (a single-step call continues a sweep's noise stream)
-static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float* zt, int B, int n,
-                              const float* temb_in, const float* coef, int with_noise, const float* noise,
-                              uint64_t seed, uint64_t chain_base, float* eps_log, int eps_log_steps, void* wsp,
-                              size_t wsb, void* stream, uint64_t step_offset, bool allow_graph) {
-  int rc = validate(d);
-  if (rc) return rc;
-  if (!xemb || !zt || !temb_in || !coef || B <= 0 || n <= 0) return DAMC_ERR_ARG;
-  const size_t need = carve(d, B, n, nullptr, nullptr);
-  if (!wsp || wsb < need) return DAMC_ERR_WORKSPACE;
+// ---- the per-call stages, shared by the reverse sweep and the guided sweep
+struct Stages {
+  const damc_denoiser_t* d;
   SweepWs w;
-  carve(d, B, n, reinterpret_cast<char*>(wsp), &w);
-  hipStream_t s = as_stream(stream);
-  const int S = sum_dout(d);
-  const int nt = d->ntemb, nx = d->nxemb;
+  hipStream_t s;
+  int S, nt, nx;
   int coloff[7];
-  for (int j = 0, o = 0; j < 7; ++j) {
-    coloff[j] = o;
-    o += lay_dout(d->blocks[j].dout);
-  }
   // nz % 4 != 0: out2 (dout = nz) is off the float4 paths of stages 2 and 3; they run blocks 0 .. nb - 1 as they run
   // every other denoiser's, and out2's columns come from the narrow kernels of denoiser_rows.hip
-  const bool narrow = narrow_out2(d);
-  const int nb = narrow ? 6 : 7;
-  const bool rows = narrow || rows_forced();
-  if (rows && !rows_fit(d)) return DAMC_ERR_UNSUPPORTED;
+  bool narrow;
+  int nb;
+  // the skinny precompute GEMMs read the time MLP and ctx Linears in their PyTorch layouts: no transposes
+  bool skinny;
+};
 
-  // ---- 1. pack the live weights
-  {
-    PackArgs pa;
-    long maxn = 0;
-    for (int j = 0; j < 7; ++j) {
-      const damc_csq_block_t& b = d->blocks[j];
-      PackBlock& p = pa.b[j];
-      p.wl = b.wl;
-      p.bl = b.bl;
-      p.ws = b.ws;
-      p.bs = b.bs;
-      p.wg = b.wg;
-      p.bg = b.bg;
-      p.wb = b.wb;
-      p.wctx = d->wctx[j];
-      p.bctx = d->bctx[j];
-      p.din = b.din;
-      p.dout = b.dout;
-      p.kp = kpad(b.din);
-      p.coloff = coloff[j];
-      p.w = w.w[j];
-      p.bls = w.bls[j];
-      p.wgb = w.wgb[j];
-      p.bg2 = w.bg2[j];
-      const long ntn = (b.dout + TC - 1) / TC;
-      maxn = std::max({maxn, ntn * 16 * p.kp, 2L * b.dout * b.dout, (long)(nt + nx) * b.dout});
-    }
-    pa.ntemb = nt;
-    pa.nxemb = nx;
-    pa.S = S;
-    pa.wctx_t = w.wctx_t;
-    pa.wctx_x = w.wctx_x;
-    pa.bctx = w.bctx;
-    // the skinny precompute GEMMs read the time MLP and ctx Linears in their PyTorch layouts: no transposes
-    bool sk = (nt & 15) == 0 && (nx & 3) == 0;
-    for (int j = 0; j < nb; ++j) sk = sk && (d->blocks[j].dout & 15) == 0;
-    hipLaunchKernelGGL(pack_denoiser_kernel, dim3((unsigned)((maxn + 255) / 256), 7, sk ? 2 : 3), dim3(256), 0, s, pa);
-    const long ntt = (long)nt * nt;
-    if (!sk) {
-      hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((ntt + 255) / 256)), dim3(256), 0, s, d->tw1, nt, nt, w.tw1t);
-      hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((ntt + 255) / 256)), dim3(256), 0, s, d->tw2, nt, nt, w.tw2t);
-    }
-    const long nb = (long)d->nz * (d->nz / 2);
-    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, d->bmat, d->nz, d->nz / 2,
-                       w.bmat);
-    DAMC_LAUNCH_CHECK();
+static void stages_init(Stages& st, const damc_denoiser_t* d, int B, int n, void* wsp, hipStream_t s) {
+  st.d = d;
+  carve(d, B, n, reinterpret_cast<char*>(wsp), &st.w);
+  st.s = s;
+  st.S = sum_dout(d);
+  st.nt = d->ntemb;
+  st.nx = d->nxemb;
+  for (int j = 0, o = 0; j < 7; ++j) {
+    st.coloff[j] = o;
+    o += lay_dout(d->blocks[j].dout);
   }
+  st.narrow = narrow_out2(d);
+  st.nb = st.narrow ? 6 : 7;
+  st.skinny = (st.nt & 15) == 0 && (st.nx & 3) == 0;
+  for (int j = 0; j < st.nb; ++j) st.skinny = st.skinny && (d->blocks[j].dout & 15) == 0;
+}
 
-  // ---- 2. ctx: time MLP (n rows), xemb part (B rows), c for every (step, row)
-  bool skinny = (nt & 15) == 0 && (nx & 3) == 0;
-  for (int j = 0; j < nb; ++j) skinny = skinny && (d->blocks[j].dout & 15) == 0;
-  if (narrow && !skinny) return DAMC_ERR_UNSUPPORTED;  // (validate() has checked)
-  if (skinny) {
+// ---- 1. pack the live weights
+static int stage_pack(const Stages& st) {
+  const damc_denoiser_t* d = st.d;
+  const SweepWs& w = st.w;
+  hipStream_t s = st.s;
+  const int nt = st.nt, nx = st.nx;
+  PackArgs pa;
+  long maxn = 0;
+  for (int j = 0; j < 7; ++j) {
+    const damc_csq_block_t& b = d->blocks[j];
+    PackBlock& p = pa.b[j];
+    p.wl = b.wl;
+    p.bl = b.bl;
+    p.ws = b.ws;
+    p.bs = b.bs;
+    p.wg = b.wg;
+    p.bg = b.bg;
+    p.wb = b.wb;
+    p.wctx = d->wctx[j];
+    p.bctx = d->bctx[j];
+    p.din = b.din;
+    p.dout = b.dout;
+    p.kp = kpad(b.din);
+    p.coloff = st.coloff[j];
+    p.w = w.w[j];
+    p.bls = w.bls[j];
+    p.wgb = w.wgb[j];
+    p.bg2 = w.bg2[j];
+    const long ntn = (b.dout + TC - 1) / TC;
+    maxn = std::max({maxn, ntn * 16 * p.kp, 2L * b.dout * b.dout, (long)(nt + nx) * b.dout});
+  }
+  pa.ntemb = nt;
+  pa.nxemb = nx;
+  pa.S = st.S;
+  pa.wctx_t = w.wctx_t;
+  pa.wctx_x = w.wctx_x;
+  pa.bctx = w.bctx;
+  hipLaunchKernelGGL(pack_denoiser_kernel, dim3((unsigned)((maxn + 255) / 256), 7, st.skinny ? 2 : 3), dim3(256), 0, s,
+                     pa);
+  const long ntt = (long)nt * nt;
+  if (!st.skinny) {
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((ntt + 255) / 256)), dim3(256), 0, s, d->tw1, nt, nt, w.tw1t);
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((ntt + 255) / 256)), dim3(256), 0, s, d->tw2, nt, nt, w.tw2t);
+  }
+  const long nbm = (long)d->nz * (d->nz / 2);
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((nbm + 255) / 256)), dim3(256), 0, s, d->bmat, d->nz, d->nz / 2,
+                     w.bmat);
+  DAMC_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- 2a. the time MLP (n rows) and its part of every block's ctx Linear: qt (n, S)
+static int stage_time(const Stages& st, const float* temb_in, int n) {
+  const damc_denoiser_t* d = st.d;
+  const SweepWs& w = st.w;
+  hipStream_t s = st.s;
+  const int nt = st.nt, nx = st.nx, S = st.S, nb = st.nb;
+  int rc;
+  if (st.narrow && !st.skinny) return DAMC_ERR_UNSUPPORTED;  // (validate() has checked)
+  if (st.skinny) {
     SkArgs g;
     memset(&g, 0, sizeof(g));
     g.M = n;
@@ -2417,110 +2433,136 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
     g.Y = w.t2;  // the ctx Linear consumes SiLU(temb)
     if ((rc = launch_skinny(g, "sweep_pre", s))) return rc;
     g.A = w.t2;
-    g.N = narrow ? coloff[6] : S;
+    g.N = st.narrow ? st.coloff[6] : S;
     g.nseg = nb;
-    for (int j = 0; j < nb; ++j) g.seg[j] = SkSeg{d->wctx[j], d->bctx[j], (long)nt + nx, coloff[j]};
+    for (int j = 0; j < nb; ++j) g.seg[j] = SkSeg{d->wctx[j], d->bctx[j], (long)nt + nx, st.coloff[j]};
     g.silu_y = 0;
     g.Y = w.qt;
     g.ldy = S;
     if ((rc = launch_skinny(g, "sweep_pre", s))) return rc;
-    g.A = xemb;
-    g.lda = nx;
-    g.M = B;
-    g.K = nx;
-    for (int j = 0; j < nb; ++j) g.seg[j] = SkSeg{d->wctx[j] + nt, nullptr, (long)nt + nx, coloff[j]};
-    g.silu_a = 1;
-    g.Y = w.px;
-    if ((rc = launch_skinny(g, "sweep_pre", s))) return rc;
-    if (narrow) {  // out2's columns of qt and px (its padding columns zero)
+    if (st.narrow) {  // out2's columns of qt (its padding columns zero)
       const int d6 = d->blocks[6].dout, p6 = lay_dout(d6);
       if ((rc = damc::launch_narrow_linear(w.t2, nt, n, nt, 0, d->wctx[6], (long)nt + nx, d->bctx[6], d6, p6,
-                                           w.qt + coloff[6], S, s)))
-        return rc;
-      if ((rc = damc::launch_narrow_linear(xemb, nx, B, nx, 1, d->wctx[6] + nt, (long)nt + nx, nullptr, d6, p6,
-                                           w.px + coloff[6], S, s)))
+                                           w.qt + st.coloff[6], S, s)))
         return rc;
     }
-    if ((rc = launch_ctx(w.px, w.qt, n, B, S, w.cx, s))) return rc;
-  } else {
-    damc::GemmArgs g;
-    g.M = n;
-    g.N = nt;
-    g.K = nt;
-    g.k_per_z = nt;
-    g.A = temb_in;
-    g.lda = nt;
-    g.B = w.tw1t;
-    g.ldb = nt;
-    g.C = w.t1;
-    g.ldc = nt;
-    g.bias = d->tb1;
-    g.bias_mod = nt;
-    g.act = DAMC_ACT_SILU;
-    if ((rc = damc::launch_gemm(g, damc::A_DENSE, damc::EPI_BIAS_ACT, damc::O_DENSE, 1, "sweep_pre", 2.0 * n * nt * nt, s)))
-      return rc;
-    g.A = w.t1;
-    g.B = w.tw2t;
-    g.C = w.t2;
-    g.bias = d->tb2;
-    g.act = DAMC_ACT_SILU;  // the ctx Linear consumes SiLU(temb)
-    if ((rc = damc::launch_gemm(g, damc::A_DENSE, damc::EPI_BIAS_ACT, damc::O_DENSE, 1, "sweep_pre", 2.0 * n * nt * nt, s)))
-      return rc;
-    g.A = w.t2;
-    g.B = w.wctx_t;
-    g.ldb = S;
-    g.N = S;
-    g.C = w.qt;
-    g.ldc = S;
-    g.bias = w.bctx;
-    g.bias_mod = S;
-    g.act = DAMC_ACT_NONE;
-    if ((rc = damc::launch_gemm(g, damc::A_DENSE, damc::EPI_BIAS_ACT, damc::O_DENSE, 1, "sweep_pre", 2.0 * n * nt * S, s)))
-      return rc;
-    const long nxe = (long)B * nx;
-    hipLaunchKernelGGL(silu_kernel, dim3((unsigned)((nxe + 255) / 256)), dim3(256), 0, s, xemb, nxe, w.xs);
-    damc::GemmArgs h;
-    h.M = B;
-    h.N = S;
-    h.K = nx;
-    h.k_per_z = nx;
-    h.A = w.xs;
-    h.lda = nx;
-    h.B = w.wctx_x;
-    h.ldb = S;
-    h.C = w.px;
-    h.ldc = S;
-    if ((rc = damc::launch_gemm(h, damc::A_DENSE, damc::EPI_STORE, damc::O_DENSE, 1, "sweep_pre", 2.0 * B * nx * S, s)))
-      return rc;
-    if ((rc = launch_ctx(w.px, w.qt, n, B, S, w.cx, s))) return rc;
+    return 0;
   }
+  damc::GemmArgs g;
+  g.M = n;
+  g.N = nt;
+  g.K = nt;
+  g.k_per_z = nt;
+  g.A = temb_in;
+  g.lda = nt;
+  g.B = w.tw1t;
+  g.ldb = nt;
+  g.C = w.t1;
+  g.ldc = nt;
+  g.bias = d->tb1;
+  g.bias_mod = nt;
+  g.act = DAMC_ACT_SILU;
+  if ((rc = damc::launch_gemm(g, damc::A_DENSE, damc::EPI_BIAS_ACT, damc::O_DENSE, 1, "sweep_pre", 2.0 * n * nt * nt, s)))
+    return rc;
+  g.A = w.t1;
+  g.B = w.tw2t;
+  g.C = w.t2;
+  g.bias = d->tb2;
+  g.act = DAMC_ACT_SILU;  // the ctx Linear consumes SiLU(temb)
+  if ((rc = damc::launch_gemm(g, damc::A_DENSE, damc::EPI_BIAS_ACT, damc::O_DENSE, 1, "sweep_pre", 2.0 * n * nt * nt, s)))
+    return rc;
+  g.A = w.t2;
+  g.B = w.wctx_t;
+  g.ldb = S;
+  g.N = S;
+  g.C = w.qt;
+  g.ldc = S;
+  g.bias = w.bctx;
+  g.bias_mod = S;
+  g.act = DAMC_ACT_NONE;
+  return damc::launch_gemm(g, damc::A_DENSE, damc::EPI_BIAS_ACT, damc::O_DENSE, 1, "sweep_pre", 2.0 * n * nt * S, s);
+}
 
-  // ---- 3. every block's gate and hyper bias for every (step, row): [sigmoid(c Wg^T + bg) | c Wb^T]
+// ---- 2b. the xemb part of every block's ctx Linear: px (M, S) = SiLU(xemb) Wx^T of M embedding rows (xs: M x nxemb
+// of scratch where the skinny GEMM does not apply)
+static int stage_px(const Stages& st, const float* xemb, int M, float* xs, float* px) {
+  const damc_denoiser_t* d = st.d;
+  const SweepWs& w = st.w;
+  hipStream_t s = st.s;
+  const int nt = st.nt, nx = st.nx, S = st.S, nb = st.nb;
+  int rc;
+  if (st.skinny) {
+    SkArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = xemb;
+    g.lda = nx;
+    g.M = M;
+    g.K = nx;
+    g.N = st.narrow ? st.coloff[6] : S;
+    g.nseg = nb;
+    for (int j = 0; j < nb; ++j) g.seg[j] = SkSeg{d->wctx[j] + nt, nullptr, (long)nt + nx, st.coloff[j]};
+    g.silu_a = 1;
+    g.Y = px;
+    g.ldy = S;
+    if ((rc = launch_skinny(g, "sweep_pre", s))) return rc;
+    if (st.narrow) {  // out2's columns of px (its padding columns zero)
+      const int d6 = d->blocks[6].dout, p6 = lay_dout(d6);
+      if ((rc = damc::launch_narrow_linear(xemb, nx, M, nx, 1, d->wctx[6] + nt, (long)nt + nx, nullptr, d6, p6,
+                                           px + st.coloff[6], S, s)))
+        return rc;
+    }
+    return 0;
+  }
+  const long nxe = (long)M * nx;
+  hipLaunchKernelGGL(silu_kernel, dim3((unsigned)((nxe + 255) / 256)), dim3(256), 0, s, xemb, nxe, xs);
+  damc::GemmArgs h;
+  h.M = M;
+  h.N = S;
+  h.K = nx;
+  h.k_per_z = nx;
+  h.A = xs;
+  h.lda = nx;
+  h.B = w.wctx_x;
+  h.ldb = S;
+  h.C = px;
+  h.ldc = S;
+  return damc::launch_gemm(h, damc::A_DENSE, damc::EPI_STORE, damc::O_DENSE, 1, "sweep_pre", 2.0 * M * nx * S, s);
+}
+
+// ---- 3. every block's gate and hyper bias for M (step, row) pairs: gh (M, 2S) = [sigmoid(c Wg^T + bg) | c Wb^T] of
+// cx (M, S).  Every engine below computes a row by itself, whatever M it runs with.
+static int stage_hyper(const Stages& st, const float* cx, float* gh, long M) {
+  const damc_denoiser_t* d = st.d;
+  const SweepWs& w = st.w;
+  hipStream_t s = st.s;
+  const int S = st.S, nb = st.nb;
+  const int* coloff = st.coloff;
+  int rc;
   damc::GemmArgs hg[7];
   double hflops = 0.0;
   for (int j = 0; j < nb; ++j) {
     const int dout = d->blocks[j].dout;
     damc::GemmArgs& g = hg[j];
-    g.M = n * B;
+    g.M = (int)M;
     g.N = 2 * dout;
     g.K = dout;
     g.k_per_z = dout;
-    g.A = w.cx + coloff[j];
+    g.A = cx + coloff[j];
     g.lda = S;
     g.B = w.wgb[j];
     g.ldb = 2 * dout;
-    g.C = w.gh + 2 * coloff[j];
+    g.C = gh + 2 * coloff[j];
     g.ldc = 2L * S;
     g.bias = w.bg2[j];
     g.bias_mod = 2 * dout;
     g.gate_cols = dout;
-    hflops += 2.0 * n * B * dout * 2.0 * dout;
+    hflops += 2.0 * M * dout * 2.0 * dout;
   }
   // round 5: on the limb product (hyper_x3_kernel) where every block fits it; DAMC_SWEEP_HYPER=fp32 (read per call)
   // keeps the fp32-MFMA engine below
   const char* hye = getenv("DAMC_SWEEP_HYPER");
-  bool hy_ok = !(hye && strcmp(hye, "fp32") == 0) && (S % 4 == 0) && ((uintptr_t)w.cx % 16 == 0) &&
-               ((uintptr_t)w.gh % 16 == 0);
+  bool hy_ok = !(hye && strcmp(hye, "fp32") == 0) && (S % 4 == 0) && ((uintptr_t)cx % 16 == 0) &&
+               ((uintptr_t)gh % 16 == 0);
   HyperGroup hgp{};
   hgp.n = nb;
   {
@@ -2533,14 +2575,14 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
     hy_ok = dout % 32 == 0 && dout <= HY_NTMAX * HY_KT && bk.wg && bk.wb && (uintptr_t)bk.wg % 16 == 0 &&
             (uintptr_t)bk.wb % 16 == 0 && coloff[j] % 4 == 0;
     HyperBlock& h = hgp.b[j];
-    h.a = w.cx + coloff[j];
+    h.a = cx + coloff[j];
     h.lda = S;
     h.wg = bk.wg;
     h.wb = bk.wb;
     h.bg = bk.bg;
-    h.c = w.gh + 2 * coloff[j];
+    h.c = gh + 2 * coloff[j];
     h.ldc = 2L * S;
-    h.M = n * B;
+    h.M = (int)M;
     h.dout = dout;
     h.ntn = 2 * dout / HY_BN;
     h.tile0 = hgp.tiles;
@@ -2569,56 +2611,97 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
     for (int j = 0; j < nb; ++j) {
       const int dout = d->blocks[j].dout;
       if ((rc = damc::launch_gemm(hg[j], damc::A_DENSE, damc::EPI_GATE, damc::O_DENSE, 1, "sweep_hyper",
-                                  2.0 * n * B * dout * 2.0 * dout, s)))
+                                  2.0 * M * dout * 2.0 * dout, s)))
         return rc;
     }
   } else if (rc) {
     return rc;
   }
-  if (narrow) {  // out2's gate and hyper bias (K = N = nz), with the exact sigmoid
+  if (st.narrow) {  // out2's gate and hyper bias (K = N = nz), with the exact sigmoid
     const damc_csq_block_t& bk = d->blocks[6];
-    if ((rc = damc::launch_narrow_hyper(w.cx + coloff[6], S, (long)n * B, bk.dout, bk.wg, bk.bg, bk.wb,
-                                        w.gh + 2 * coloff[6], 2L * S, s)))
+    if ((rc = damc::launch_narrow_hyper(cx + coloff[6], S, M, bk.dout, bk.wg, bk.bg, bk.wb, gh + 2 * coloff[6], 2L * S,
+                                        s)))
       return rc;
   }
+  return 0;
+}
+
+// ---- 4 (row-resident, denoiser_rows.hip): one launch, each workgroup runs every step and block of its rows on the
+// caller's zt in place; the call's values travel in the kernel arguments
+static int rows_args(const Stages& st, damc::RowsArgs& ra, float* zt, int B, int n, const float* coef, int with_noise,
+                     const float* noise, uint64_t seed, uint64_t chain_base, uint64_t step_offset, float* eps_log,
+                     int eps_log_steps) {
+  const damc_denoiser_t* d = st.d;
+  memset(&ra, 0, sizeof(ra));
+  ra.ld = rows_ld(d, ra.b);
+  for (int j = 0; j < 7; ++j) {
+    const damc_csq_block_t& bk = d->blocks[j];
+    damc::RowsBlock& p = ra.b[j];
+    p.w = st.w.w[j];
+    p.bls = st.w.bls[j];
+    p.din = bk.din;
+    p.kp = kpad(bk.din);
+    p.dout = bk.dout;
+    p.ntn = (bk.dout + TC - 1) / TC;
+    p.ghoff = 2 * st.coloff[j];
+  }
+  ra.bmat = st.w.bmat;
+  ra.nz = d->nz;
+  ra.B = B;
+  ra.n = n;
+  ra.residual = d->residual;
+  ra.gh = st.w.gh;
+  ra.ldgh = 2L * st.S;
+  ra.zt = zt;
+  ra.noise = (with_noise && noise) ? noise : nullptr;
+  ra.eps_log = eps_log;
+  ra.eps_log_steps = eps_log ? eps_log_steps : 0;
+  ra.seed = seed;
+  ra.chain_base = chain_base;
+  ra.step_offset = step_offset;
+  ra.with_noise = with_noise ? 1 : 0;
+  return step_table(coef, n, st.s, &ra.tab);
+}
+
+static double rows_flops(const damc_denoiser_t* d, double rows, int n) {
+  double fl = 0;
+  for (int j = 0; j < 7; ++j) fl += 2.0 * rows * 2.0 * d->blocks[j].din * d->blocks[j].dout;
+  return fl * n;
+}
+
+// step_offset: Philox step index of the first noisy step (a single-step call continues a sweep's noise stream)
+static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float* zt, int B, int n,
+                              const float* temb_in, const float* coef, int with_noise, const float* noise,
+                              uint64_t seed, uint64_t chain_base, float* eps_log, int eps_log_steps, void* wsp,
+                              size_t wsb, void* stream, uint64_t step_offset, bool allow_graph) {
+  int rc = validate(d);
+  if (rc) return rc;
+  if (!xemb || !zt || !temb_in || !coef || B <= 0 || n <= 0) return DAMC_ERR_ARG;
+  const size_t need = carve(d, B, n, nullptr, nullptr);
+  if (!wsp || wsb < need) return DAMC_ERR_WORKSPACE;
+  hipStream_t s = as_stream(stream);
+  Stages st;
+  stages_init(st, d, B, n, wsp, s);
+  const SweepWs& w = st.w;
+  const int S = st.S;
+  const bool rows = st.narrow || rows_forced();
+  if (rows && !rows_fit(d)) return DAMC_ERR_UNSUPPORTED;
+
+  // ---- 1-3: the weights, then everything that does not depend on zt: ctx c for every (step, row) from the time MLP
+  // (n rows) and the xemb part (B rows), and every block's gate and hyper bias
+  if ((rc = stage_pack(st))) return rc;
+  if ((rc = stage_time(st, temb_in, n))) return rc;
+  if ((rc = stage_px(st, xemb, B, w.xs, w.px))) return rc;
+  if ((rc = launch_ctx(w.px, 0, w.qt, n, B, S, w.cx, s))) return rc;
+  if ((rc = stage_hyper(st, w.cx, w.gh, (long)n * B))) return rc;
 
   // ---- 4. the dependent chain
   if (rows) {
-    // row-resident (denoiser_rows.hip): one launch, each workgroup runs every step and block of its 16 rows on the
-    // caller's zt in place; the call's values travel in the kernel arguments
     damc::RowsArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.ld = rows_ld(d, ra.b);
-    for (int j = 0; j < 7; ++j) {
-      const damc_csq_block_t& bk = d->blocks[j];
-      damc::RowsBlock& p = ra.b[j];
-      p.w = w.w[j];
-      p.bls = w.bls[j];
-      p.din = bk.din;
-      p.kp = kpad(bk.din);
-      p.dout = bk.dout;
-      p.ntn = (bk.dout + TC - 1) / TC;
-      p.ghoff = 2 * coloff[j];
-    }
-    ra.bmat = w.bmat;
-    ra.nz = d->nz;
-    ra.B = B;
-    ra.n = n;
-    ra.residual = d->residual;
-    ra.gh = w.gh;
-    ra.ldgh = 2L * S;
-    ra.zt = zt;
-    ra.noise = (with_noise && noise) ? noise : nullptr;
-    ra.eps_log = eps_log;
-    ra.eps_log_steps = eps_log ? eps_log_steps : 0;
-    ra.seed = seed;
-    ra.chain_base = chain_base;
-    ra.step_offset = step_offset;
-    ra.with_noise = with_noise ? 1 : 0;
-    if ((rc = step_table(coef, n, s, &ra.tab))) return rc;
-    double fl = 0;
-    for (int j = 0; j < 7; ++j) fl += 2.0 * B * 2.0 * d->blocks[j].din * d->blocks[j].dout;
-    ProfScope ps("denoise_chain", fl * n, s);
+    if ((rc = rows_args(st, ra, zt, B, n, coef, with_noise, noise, seed, chain_base, step_offset, eps_log,
+                        eps_log_steps)))
+      return rc;
+    ProfScope ps("denoise_chain", rows_flops(d, B, n), s);
     return damc::launch_sweep_rows(ra, s);
   }
   SweepCall call;
@@ -2701,4 +2784,88 @@ extern "C" int damc_denoise_step(const damc_denoiser_t* d, const float* xemb, fl
                                  void* stream) {
   return reverse_sweep_impl(d, xemb, zt, B, 1, temb_row, coef_row, with_noise, noise, seed, chain_base, eps,
                             eps ? 1 : 0, wsp, wsb, stream, noise_step, false);
+}
+
+// ------------------------------------------------------------------------------------- the guided sweep
+// Classifier-free guidance (_netQ_U.forward with cond_w > 0, workspace/src/diffusion_net.py:595-620) as one sweep: the
+// reference evaluates the denoiser twice per step, on the encoder's xemb and on a fresh prior_emb(randn), and steps on
+// (1 + w) eps_c - w eps_u.  The conditional planes (px, cx, gh) are the reverse sweep's.  The unconditional context
+// changes every step, so its planes are per (step, row) throughout: px_u (n B, S) by the same GEMM with M = n B, cx_u
+// by the same ctx kernel with px strided per step, gh_u by the same hyper stage; the same kernels for both branches,
+// each computing a row by itself, so a row's gate does not depend on the plane or batch it sits in.  The chain is the
+// twin-row form of denoiser_rows.hip: always row-resident, no team, no launch chain.
+// Workspace beyond the reverse sweep's: px_u, cx_u (S each) and gh_u (2 S) floats per (step, row), plus nxemb for
+// SiLU(xemb_unc) where the skinny GEMM does not apply: 4 S = 5632 floats at the CIFAR widths, ~0.3 GB at B = 128,
+// n = 100 (xemb_unc itself, the caller's, is another n B nxemb floats).
+namespace {
+struct GuidedWs {
+  float *px_u, *cx_u, *gh_u, *xs_u;
+};
+
+bool guided_ok(const damc_denoiser_t* d) { return !validate(d) && !narrow_out2(d) && rows_fit(d); }
+
+size_t carve_guided(const damc_denoiser_t* d, int B, int n, char* base, GuidedWs* g) {
+  size_t off = carve(d, B, n, nullptr, nullptr);
+  auto take = [&](long floats) -> float* {
+    float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
+    off += ((size_t)floats * sizeof(float) + 255) / 256 * 256;
+    return p;
+  };
+  const long S = sum_dout(d), M = (long)n * B;
+  bool skinny = (d->ntemb & 15) == 0 && (d->nxemb & 3) == 0;
+  for (int j = 0; j < 7; ++j) skinny = skinny && (d->blocks[j].dout & 15) == 0;
+  GuidedWs t;
+  t.px_u = take(M * S);
+  t.cx_u = take(M * S);
+  t.gh_u = take(M * 2 * S);
+  t.xs_u = take(skinny ? 0 : M * d->nxemb);
+  if (g) *g = t;
+  return off;
+}
+}  // namespace
+
+extern "C" size_t damc_guided_sweep_workspace_bytes(const damc_denoiser_t* d, int B, int n) {
+  if (B <= 0 || n <= 0 || !guided_ok(d)) return 0;
+  return carve_guided(d, B, n, nullptr, nullptr);
+}
+
+extern "C" int damc_guided_sweep(const damc_denoiser_t* d, const float* xemb, const float* xemb_unc, float cond_w,
+                                 float* zt, int B, int n, const float* temb_in, const float* coef, int with_noise,
+                                 const float* noise, uint64_t seed, uint64_t chain_base, float* eps_log,
+                                 int eps_log_steps, void* wsp, size_t wsb, void* stream) {
+  int rc = validate(d);
+  if (rc) return rc;
+  if (!xemb || !xemb_unc || !zt || !temb_in || !coef || B <= 0 || n <= 0 || !(cond_w > 0.f)) return DAMC_ERR_ARG;
+  if (!guided_ok(d)) return DAMC_ERR_UNSUPPORTED;
+  if ((long)n * B > (1L << 30)) return DAMC_ERR_UNSUPPORTED;  // the planes' row count as the GEMMs' int M
+  const size_t need = carve_guided(d, B, n, nullptr, nullptr);
+  if (!wsp || wsb < need) return DAMC_ERR_WORKSPACE;
+  hipStream_t s = as_stream(stream);
+  Stages st;
+  stages_init(st, d, B, n, wsp, s);
+  GuidedWs gw;
+  carve_guided(d, B, n, reinterpret_cast<char*>(wsp), &gw);
+  const SweepWs& w = st.w;
+  const int S = st.S;
+  const int M = n * B;
+
+  if ((rc = stage_pack(st))) return rc;
+  if ((rc = stage_time(st, temb_in, n))) return rc;
+  // the conditional planes, as the reverse sweep's
+  if ((rc = stage_px(st, xemb, B, w.xs, w.px))) return rc;
+  if ((rc = launch_ctx(w.px, 0, w.qt, n, B, S, w.cx, s))) return rc;
+  if ((rc = stage_hyper(st, w.cx, w.gh, M))) return rc;
+  // the unconditional planes: a context per (step, row)
+  if ((rc = stage_px(st, xemb_unc, M, gw.xs_u, gw.px_u))) return rc;
+  if ((rc = launch_ctx(gw.px_u, (long)B * S, w.qt, n, B, S, gw.cx_u, s))) return rc;
+  if ((rc = stage_hyper(st, gw.cx_u, gw.gh_u, M))) return rc;
+
+  damc::RowsArgs ra;
+  if ((rc = rows_args(st, ra, zt, B, n, coef, with_noise, noise, seed, chain_base, 0, eps_log, eps_log_steps)))
+    return rc;
+  ra.gh_u = gw.gh_u;
+  ra.gw = cond_w;
+  ra.gw1 = 1.f + cond_w;  // the reference's (1 + cond_w), rounded to fp32 once
+  ProfScope ps("denoise_chain", rows_flops(d, 2.0 * B, n), s);
+  return damc::launch_sweep_rows_guided(ra, s);
 }

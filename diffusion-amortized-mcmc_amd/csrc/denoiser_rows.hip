@@ -15,6 +15,10 @@
 // LDS image of a row (floats):  [ X0: sin cos z 0.. | U | o2 | T | o1 | P | o0 ]  kp0 + 10 w (o0 up to in1's padded K),
 // + 4 of padding so the 16 rows of a ds_read_b128 fall on distinct banks.  in0 reads X0 and writes o0, in1 o0 -> o1, in2 o1 -> o2,
 // mid o2 -> U, out0 [U | o2] -> T, out1 [T | o1] -> P, out2 [P | o0] -> z (inside X0): every cat() is one K range.
+//
+// The guided sweep (classifier-free guidance, diffusion_net.py:595-620) is the same kernel with GUIDED set: a workgroup
+// owns 8 latent rows and holds each twice, image rows 0-7 on the conditional gates and 8-15 on the unconditional ones,
+// so every weight fragment serves both evaluations of a step; the twins exchange eps in the last block's epilogue.
 #include "denoiser_rows.h"
 
 namespace damc {
@@ -25,7 +29,10 @@ constexpr int RW_WAVES = 4, RW_THREADS = 64 * RW_WAVES;
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // block j of step k for the workgroup's 16 rows: out = (x Wl^T + bl) gate + hb + (x Ws^T + bs), x = lrelu(src) (in0: src)
-template <bool EMB, bool FINAL>
+// GUIDED (classifier-free guidance, diffusion_net.py:603-606): image rows lr and lr + 8 are the conditional and the
+// unconditional evaluation of latent row r0 + (lr & 7); they differ in the plane their gates come from, and meet in
+// the FINAL epilogue
+template <bool EMB, bool FINAL, bool GUIDED>
 __device__ __forceinline__ void rows_block(const RowsArgs& a, const RowsBlock& b, float* lds, int k, int r0,
                                            const float* tb) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -52,10 +59,11 @@ __device__ __forceinline__ void rows_block(const RowsArgs& a, const RowsBlock& b
       bias[i] = (i == 0 || two) ? b.bls[ti * 16 + m] : 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = r0 + 4 * q + r;
+        const int row = GUIDED ? r0 + ((4 * q + r) & 7) : r0 + 4 * q + r;
         gate[i][r] = hb[i][r] = 0.f;
         if (cok && row < a.B) {
-          const float* ghr = a.gh + ((long)k * a.B + row) * a.ldgh + b.ghoff + c;
+          const float* plane = (GUIDED && 4 * q + r >= 8) ? a.gh_u : a.gh;
+          const float* ghr = plane + ((long)k * a.B + row) * a.ldgh + b.ghoff + c;
           gate[i][r] = ghr[0];
           hb[i][r] = ghr[b.dout];
         }
@@ -108,7 +116,7 @@ __device__ __forceinline__ void rows_block(const RowsArgs& a, const RowsBlock& b
       if (!((i == 0 || two) && m < 8 && c < b.dout)) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int lr = 4 * q + r, row = r0 + lr;
+        const int lr = 4 * q + r, row = GUIDED ? r0 + (lr & 7) : r0 + lr;
         // ConcatSquashLinearSkipCtx.forward, the fma spelled out as in chain_kernel: every sweep form rounds alike
         const float o = __builtin_fmaf(s[r] + bl, gate[i][r], hb[i][r]) + (sk[r] + bs);
         float* dst = lds + lr * LD + b.dst + c;
@@ -118,9 +126,17 @@ __device__ __forceinline__ void rows_block(const RowsArgs& a, const RowsBlock& b
         }
         // reverse step (diffusion_net.py:601-620): eps = z + out; pred = c0 (z - eps c1)
         const float zv = *dst;
-        const float eps = a.residual ? zv + o : o;
+        float eps = a.residual ? zv + o : o;
+        if (GUIDED) {
+          // the twin's eps of this column sits in lane ^ 32 (rows 4 (lane >> 4) + r; the pair shares m and c, so both
+          // lanes are here); (1 + cond_w) * eps_pred - cond_w * eps_pred_unc, each op rounded, in both twins
+          const float other = __shfl_xor(eps, 32, 64);
+          const float ec = lr < 8 ? eps : other, eu = lr < 8 ? other : eps;
+          eps = sub_rn(mul_rn(a.gw1, ec), mul_rn(a.gw, eu));
+        }
         const bool last = tb[5] != 0.f;
-        if (row < a.B && a.eps_log && k < a.eps_log_steps) a.eps_log[((long)k * a.B + row) * a.nz + c] = eps;
+        if ((!GUIDED || lr < 8) && row < a.B && a.eps_log && k < a.eps_log_steps)
+          a.eps_log[((long)k * a.B + row) * a.nz + c] = eps;
         const float pred = mul_rn(tb[0], sub_rn(zv, mul_rn(eps, tb[1])));
         float zn = pred;
         if (!last) {
@@ -146,15 +162,19 @@ __device__ __forceinline__ void rows_block(const RowsArgs& a, const RowsBlock& b
   __syncthreads();
 }
 
+// GUIDED: the workgroup's 16 image rows are its 8 latent rows twice (rows_block); both twins start every step from
+// the same z, so the embedding below is evaluated per image row like everything else
+template <bool GUIDED>
 __global__ __launch_bounds__(RW_THREADS) void sweep_rows_kernel(RowsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // [16][a.ld]
   const int tid = threadIdx.x;
-  const int r0 = blockIdx.x * ROWS_TM;
+  const int r0 = blockIdx.x * (GUIDED ? ROWS_GTM : ROWS_TM);
   const int nz = a.nz, half = nz >> 1, LD = a.ld;
   const int zoff = 2 * half;  // z within X0
   for (int i = tid; i < ROWS_TM * nz; i += RW_THREADS) {
     const int r = i / nz, c = i - r * nz;
-    lds[r * LD + zoff + c] = r0 + r < a.B ? a.zt[(long)(r0 + r) * nz + c] : 0.f;
+    const int row = GUIDED ? r0 + (r & 7) : r0 + r;
+    lds[r * LD + zoff + c] = row < a.B ? a.zt[(long)row * nz + c] : 0.f;
   }
   __syncthreads();
   // in0's Fourier embedding: up to four (row, column) outputs of zB per thread, their k loops interleaved
@@ -194,12 +214,12 @@ __global__ __launch_bounds__(RW_THREADS) void sweep_rows_kernel(RowsArgs a) {
       }
     }
     __syncthreads();
-    rows_block<true, false>(a, a.b[0], lds, k, r0, tb);
+    rows_block<true, false, GUIDED>(a, a.b[0], lds, k, r0, tb);
 #pragma unroll 1
-    for (int j = 1; j < 6; ++j) rows_block<false, false>(a, a.b[j], lds, k, r0, tb);
-    rows_block<false, true>(a, a.b[6], lds, k, r0, tb);
+    for (int j = 1; j < 6; ++j) rows_block<false, false, GUIDED>(a, a.b[j], lds, k, r0, tb);
+    rows_block<false, true, GUIDED>(a, a.b[6], lds, k, r0, tb);
   }
-  for (int i = tid; i < ROWS_TM * nz; i += RW_THREADS) {
+  for (int i = tid; i < (GUIDED ? ROWS_GTM : ROWS_TM) * nz; i += RW_THREADS) {
     const int r = i / nz, c = i - r * nz;
     if (r0 + r < a.B) a.zt[(long)(r0 + r) * nz + c] = lds[r * LD + zoff + c];
   }
@@ -253,18 +273,31 @@ int rows_layout(int nz, int w, int kp0, RowsBlock* b) {
   return o0 + (w + 63) / 64 * 64 + 4;  // in1 reads o0 over its padded K
 }
 
-int launch_sweep_rows(const RowsArgs& a, hipStream_t s) {
+namespace {
+
+template <bool GUIDED>
+int launch_rows(const RowsArgs& a, hipStream_t s) {
   const size_t smem = (size_t)ROWS_TM * a.ld * sizeof(float);
   if (smem > ROWS_LDS_MAX || (a.ld & 3) || a.nz > 128 || (a.nz & 1)) return DAMC_ERR_UNSUPPORTED;
   for (int j = 0; j < 7; ++j)
     if ((a.b[j].kp & 63) || (a.b[j].din & 3) || a.b[j].din > a.b[j].kp || ((a.b[j].src | (j < 6 ? a.b[j].dst : 0)) & 3) ||
         a.b[j].src + a.b[j].kp > a.ld)
       return DAMC_ERR_UNSUPPORTED;
-  static const bool lds_ok = hipFuncSetAttribute((const void*)sweep_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)ROWS_LDS_MAX) == hipSuccess;
+  static const bool lds_ok = hipFuncSetAttribute((const void*)sweep_rows_kernel<GUIDED>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROWS_LDS_MAX) == hipSuccess;
   if (!lds_ok) return DAMC_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(sweep_rows_kernel, dim3((unsigned)((a.B + ROWS_TM - 1) / ROWS_TM)), dim3(RW_THREADS), smem, s, a);
+  const int tm = GUIDED ? ROWS_GTM : ROWS_TM;
+  hipLaunchKernelGGL(sweep_rows_kernel<GUIDED>, dim3((unsigned)((a.B + tm - 1) / tm)), dim3(RW_THREADS), smem, s, a);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+int launch_sweep_rows(const RowsArgs& a, hipStream_t s) { return launch_rows<false>(a, s); }
+
+int launch_sweep_rows_guided(const RowsArgs& a, hipStream_t s) {
+  if (!a.gh_u) return DAMC_ERR_ARG;
+  return launch_rows<true>(a, s);
 }
 
 int launch_narrow_linear(const float* A, long lda, int M, int K, int silu_a, const float* W, long ldw, const float* bias,

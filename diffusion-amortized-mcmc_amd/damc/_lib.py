@@ -232,6 +232,9 @@ _SIGS = {
                                   _SZ, _P]),
     "damc_denoise_step": (_I, [ctypes.POINTER(Denoiser), _P, _P, _I, _P, _P, _I, _P, _U64, _U64, _U64, _P, _P, _SZ,
                                _P]),
+    "damc_guided_sweep_workspace_bytes": (_SZ, [ctypes.POINTER(Denoiser), _I, _I]),
+    "damc_guided_sweep": (_I, [ctypes.POINTER(Denoiser), _P, _P, _F, _P, _I, _I, _P, _P, _I, _P, _U64, _U64, _P, _I,
+                               _P, _SZ, _P]),
     "damc_ebm_grad": (_I, [ctypes.POINTER(Ebm), _P, _I, _P, _P, _P]),
     "damc_adam_chunk_bytes": (_SZ, []),
     "damc_adam_chunk_count": (_I, [ctypes.POINTER(ctypes.c_longlong), _I]),

@@ -4,6 +4,7 @@ Mirrors ``_netQ_U.forward`` (workspace/src/diffusion_net.py:585-622):
   x given : xemb = encoder(x)                 -> Encoder_* on the MFMA conv engine + fused IN/LReLU
   x None  : xemb = prior_emb(randn(b, nz))    -> two GEMMs (LeakyReLU 0.01 between)
   zt = randn(b, nz) (host generator, as the reference) then n_interval reverse steps in libdamc.
+  cond_w > 0 : classifier-free guidance, both denoiser evaluations of every step in one damc_guided_sweep call.
 The toy's _netQ_U_toy (workspace/toy_example/src/diffusion_net.py:141-239) takes the same route: its MLP encoder and
 its prior_emb (nz = 2) run as one fused launch (damc_mlp_forward), its sweep in the library's row-resident form.
 
@@ -225,6 +226,7 @@ class DenoiserPlan:
             raise NotImplementedError("Diffusion_UnetA with %d blocks" % len(self.blocks))
         self.nz, self.ntemb, self.nxemb = p.nz, p.ntemb, p.nxemb
         self._ws = None
+        self._gws = None
 
     def pack(self, device):
         from .training import _denoiser_desc, _denoiser_params
@@ -240,6 +242,16 @@ class DenoiserPlan:
         if self._ws is None:
             self._ws = _lib.WorkspaceCache()
         return self._ws.get(device, nbytes, (int(B), int(n))), nbytes
+
+    def guided_workspace(self, desc, B, n, device):
+        """The guided sweep's workspace (its own cache: a guided and an unguided call do not evict each other), or
+        (None, 0) where the library has no guided sweep for this denoiser."""
+        nbytes = int(_lib.lib().damc_guided_sweep_workspace_bytes(ctypes.byref(desc), B, n))
+        if nbytes == 0:
+            return None, 0
+        if self._gws is None:
+            self._gws = _lib.WorkspaceCache()
+        return self._gws.get(device, nbytes, (int(B), int(n))), nbytes
 
 
 _ENC = weakref.WeakKeyDictionary()
@@ -354,18 +366,68 @@ def reverse_sweep(Q, xemb, zt, noise=None, seed=None, chain_base=0, eps_log_step
     return eps_log
 
 
+STREAM_GUIDE = 0x54  # DAMC_STREAM_GUIDE (csrc/common.h): the Philox stream of the guided sweep's prior-embedding noise
+
+
+def guided_sweep(Q, xemb, xemb_unc, zt, w, noise=None, seed=None, chain_base=0, eps_log_steps=0, with_noise=None):
+    """In-place guided (classifier-free guidance, cond_w = w > 0) latent reverse sweep on zt (B, nz) in one
+    damc_guided_sweep call; xemb (B, nxemb) the conditional embedding, xemb_unc (n, B, nxemb) the unconditional one of
+    every step in sweep order.  Returns the guided eps of the first eps_log_steps steps.  Mirrors reverse_sweep."""
+    dev = zt.device
+    plan = _DEN.get(Q.p)
+    if plan is None:
+        plan = _DEN[Q.p] = DenoiserPlan(Q.p)
+    d = plan.pack(dev)
+    n = int(Q.n_interval)
+    B = zt.shape[0]
+    coef_h, temb_d = cached_step_tables(n, Q.logsnr_min, Q.logsnr_max, Q.var_type, plan.ntemb, dev)
+    L = _lib.lib()
+    ws, nbytes = plan.guided_workspace(d, B, n, dev)
+    if ws is None:
+        raise _lib.DamcError("the guided sweep does not take this denoiser (its row image does not fit, or nz % 4 != 0)")
+    with_noise = bool(Q.with_noise) if with_noise is None else bool(with_noise)
+    if noise is not None:
+        noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if with_noise and noise is None else 0
+    xemb = xemb.to(dtype=torch.float32).contiguous()
+    xemb_unc = xemb_unc.to(dtype=torch.float32).contiguous()
+    if xemb_unc.numel() != n * B * plan.nxemb or xemb.numel() != B * plan.nxemb:
+        raise _lib.DamcError("xemb must be (%d, %d) and xemb_unc (%d, %d, %d)" % (B, plan.nxemb, n, B, plan.nxemb))
+    eps_log = torch.empty(max(eps_log_steps, 1), B, plan.nz, dtype=torch.float32, device=dev) if eps_log_steps else None
+    check(L.damc_guided_sweep(ctypes.byref(d), ptr(xemb), ptr(xemb_unc), float(w), ptr(zt), B, n, ptr(temb_d),
+                              coef_h.numpy().ctypes.data_as(ctypes.c_void_p), int(with_noise), ptr(noise), seed,
+                              chain_base, ptr(eps_log), int(eps_log_steps), ptr(ws), nbytes, _lib.stream_ptr(dev)),
+          "damc_guided_sweep")
+    return eps_log
+
+
+def _guided_fits(Q, b, device):
+    plan = _DEN.get(Q.p)
+    if plan is None:
+        plan = _DEN[Q.p] = DenoiserPlan(Q.p)
+    return int(_lib.lib().damc_guided_sweep_workspace_bytes(ctypes.byref(plan.pack(device)), b, int(Q.n_interval))) > 0
+
+
 def q_forward(Q, x=None, b=None, device=None, cond_w=-1, zt=None, seed=None, chain_base=0):
     """_netQ_U.forward on the HIP path (diffusion_net.py:585-622).
 
     zt / seed / chain_base (not in the reference's signature; sharded callers only): the initial latent
     (default: torch.randn(b, nz) on the host generator, as the reference), the sweep's Philox key and the
     global index of row 0 — a shard that passes its slice of the global zt, the global seed and its slice
-    start reproduces its rows of the 1-GPU sweep bit for bit."""
+    start reproduces its rows of the 1-GPU sweep bit for bit.
+
+    cond_w > 0 (classifier-free guidance, diffusion_net.py:595-620) runs the guided sweep, one launch sequence for
+    all steps.  With a seed, the per-step prior-embedding noise is the library's Philox stream 0x54 keyed by the
+    global chain index and the step noise the sweep's own in-kernel stream, so the same sharding rule holds; without
+    one, torch's draws are taken in the reference's order (_q_forward_guided)."""
     if cond_w is not None and cond_w > 0 and x is not None:
         if Q.nz % 4:
             raise NotImplementedError("classifier-free guidance (cond_w > 0) is not implemented for nz % 4 != 0 "
-                                      "(the toy amortizer): the guided step loop runs on the training kernels")
-        return _q_forward_guided(Q, x, float(cond_w))
+                                      "(the toy amortizer): the guided sweep needs float4 rows")
+        if seed is None:
+            return _q_forward_guided(Q, x, float(cond_w), zt0=zt)
+        return _q_forward_guided_seeded(Q, x, float(cond_w), zt, int(seed), int(chain_base))
     if x is not None:
         assert b is None and device is None
         b = len(x)
@@ -388,19 +450,75 @@ def q_forward(Q, x=None, b=None, device=None, cond_w=-1, zt=None, seed=None, cha
     return zt
 
 
-def _q_forward_guided(Q, x, w, eps_trace=None):
+def _initial_latent(Q, b, device, zt):
+    if zt is None:  # the reference's host-generator draw
+        return torch.randn(b, Q.nz).to(device)
+    zt = zt.to(device=device, dtype=torch.float32).clone()
+    if zt.shape != (b, Q.nz):
+        raise _lib.DamcError("zt must be (%d, %d)" % (b, Q.nz))
+    return zt
+
+
+def _q_forward_guided(Q, x, w, eps_trace=None, zt0=None):
+    """Classifier-free guidance (cond_w > 0, diffusion_net.py:595-620) on the guided sweep, with the reference's
+    draws: torch's, taken before the sweep in the reference's order and with its calls (none depends on zt): the host
+    randn(b, nz) for zt, then for i = n-1 .. 0 the device randn(b, nz) of the step's prior embedding and, for
+    i != 0, the step's randn_like(zt).  All n prior embeddings are one prior_embedding call over n b rows, handed to
+    damc_guided_sweep as xemb_unc with the step noise injected.  eps_trace (tests): a list that receives each step's
+    guided eps.  A denoiser the guided sweep does not take runs the step loop (_q_forward_guided_steps)."""
+    b, device, n = len(x), x.device, int(Q.n_interval)
+    if device.type != "cuda":
+        raise _lib.DamcError("the HIP sweep needs a ROCm device (got %s)" % device)
+    if not _guided_fits(Q, b, device):
+        return _q_forward_guided_steps(Q, x, w, eps_trace, zt0=zt0)
+    xemb = encoder_forward(Q.encoder, x)
+    zt = _initial_latent(Q, b, device, zt0)
+    pe, steps = [], []
+    for i in reversed(range(0, n)):
+        pe.append(torch.randn(b, Q.nz, device=device))
+        if i != 0:
+            steps.append(torch.randn_like(zt))
+    xemb_unc = prior_embedding(Q, torch.cat(pe, 0))
+    noise = torch.stack(steps, 0) if steps and Q.with_noise else None
+    eps = guided_sweep(Q, xemb, xemb_unc, zt, w, noise=noise, seed=0,
+                       eps_log_steps=n if eps_trace is not None else 0)
+    if eps_trace is not None:
+        eps_trace.extend(eps[k].clone() for k in range(n))
+    return zt
+
+
+def _q_forward_guided_seeded(Q, x, w, zt, seed, chain_base):
+    """The guided sweep on the library's Philox streams: the prior-embedding noise of (step k, row) is stream 0x54 at
+    (seed, chain_base + row, k), the step noise the sweep's in-kernel stream.  Both are keyed by the global chain
+    index, so a shard reproduces its rows of the whole batch's sweep bit for bit."""
+    from .langevin import philox_normal
+
+    b, device, n = len(x), x.device, int(Q.n_interval)
+    if device.type != "cuda":
+        raise _lib.DamcError("the HIP sweep needs a ROCm device (got %s)" % device)
+    xemb = encoder_forward(Q.encoder, x)
+    zt = _initial_latent(Q, b, device, zt)
+    pn = philox_normal(n, b, Q.nz, seed, device, step_offset=0, chain_base=chain_base, stream_id=STREAM_GUIDE)
+    xemb_unc = prior_embedding(Q, pn.view(n * b, Q.nz))
+    guided_sweep(Q, xemb, xemb_unc, zt, w, seed=seed, chain_base=chain_base)
+    return zt
+
+
+def _q_forward_guided_steps(Q, x, w, eps_trace=None, zt0=None):
     """Classifier-free guidance (cond_w > 0, diffusion_net.py:595-620; round 5): the reference's step loop with its
     draws in its order (zt from the host generator, then per step a fresh prior embedding's noise and the step's
     noise on the device), each step's two denoiser evaluations on libdamc (Diffusion_UnetA.forward ->
     damc.training.denoiser_apply, the training kernels' forward) and the prior embedding on damc_gemm; the guidance
     combination and the schedule algebra are the reference's own tensor formulas (src/diffusion_helper_func.py).
-    Unlike the unguided sweep (one team launch), this runs one denoiser launch sequence per evaluation: the
-    reference's drivers never set cond_w.  eps_trace (tests): a list that receives each step's guided eps_pred."""
+    This runs one denoiser launch sequence per evaluation: it is the comparator of the guided sweep
+    (_q_forward_guided) in the tests, and the path of a denoiser whose row image does not fit the guided sweep.
+    eps_trace (tests): a list that receives each step's guided eps_pred.  zt0: the initial latent in place of the
+    host draw (which is then not taken)."""
     from src.diffusion_helper_func import diffusion_reverse, logsnr_schedule_fn, pred_x_from_eps
 
     b, device, n = len(x), x.device, int(Q.n_interval)
     xemb = encoder_forward(Q.encoder, x)
-    zt = torch.randn(b, Q.nz).to(device)
+    zt = torch.randn(b, Q.nz).to(device) if zt0 is None else zt0.to(device=device, dtype=torch.float32).clone()
     for i in reversed(range(0, n)):
         i_tensor = torch.ones(b, dtype=torch.float).to(device) * float(i)
         logsnr_t = logsnr_schedule_fn(i_tensor / (n - 1.0), logsnr_min=Q.logsnr_min, logsnr_max=Q.logsnr_max)

@@ -429,6 +429,30 @@ long damc_sweep_team_failures(int device);
 int damc_denoise_step(const damc_denoiser_t* d, const float* xemb, float* zt, int batch, const float* temb_row,
                       const float* coef_row, int with_noise, const float* noise, uint64_t seed, uint64_t noise_step,
                       uint64_t chain_base, float* eps, void* workspace, size_t workspace_bytes, void* stream);
+/* The guided reverse sweep: classifier-free guidance, Q(x, cond_w = w > 0) (workspace/src/diffusion_net.py:595-620), as
+ * ONE stream-ordered call.  Per step the reference evaluates the denoiser on the encoder's xemb and on a fresh
+ * prior_emb(randn) and steps on eps = (1 + w) eps_c - w eps_u (each op rounded to fp32).  xemb (B, nxemb) is the
+ * conditional embedding; xemb_unc (n_steps, B, nxemb) the unconditional one of every step, step-major in sweep order
+ * (k = n_steps-1-i), made by the caller.  A seeded caller draws its noise from damc_philox_normal with stream_id
+ * 0x54 (DAMC_STREAM_GUIDE; keyed seed, chain_base + row, step k) and passes it through prior_emb as n_steps * B rows;
+ * the library draws only the step noise, from the sweep's own stream (0x53), keyed by the latent row as
+ * damc_reverse_sweep keys it, so shards by chain_base reproduce their rows bit for bit.
+ * The per-call stages are the reverse sweep's, run for both branches by the same kernels (the unconditional planes per
+ * (step, row)); the chain runs row-resident with each latent row held twice: a workgroup owns 8 latent rows, its MFMA
+ * rows 0-7 their conditional and 8-15 their unconditional evaluation, every weight fragment serving both, and the two
+ * eps meet by one cross-lane move in the last block's epilogue (denoiser_rows.hip).  No allocation, no
+ * synchronisation; zt (B, nz) is updated in place; coef is a HOST pointer; temb_in, coef, with_noise, noise
+ * (n_steps-1, B, nz), seed, chain_base, eps_log (the guided eps of the first eps_log_steps steps) as
+ * damc_reverse_sweep's.
+ * workspace: damc_guided_sweep_workspace_bytes, the reverse sweep's plus 4 S floats per (step, row) for the
+ * unconditional planes (S = the blocks' summed widths: ~0.3 GB more at B = 128, 100 steps, the CIFAR widths).  It is 0
+ * where the 16-row LDS image does not fit the CU or nz % 4 != 0; the sweep then returns DAMC_ERR_UNSUPPORTED.
+ * DAMC_ERR_ARG: a null xemb, xemb_unc, zt, temb_in or coef, a non-positive size, cond_w <= 0. */
+size_t damc_guided_sweep_workspace_bytes(const damc_denoiser_t* d, int batch, int n_steps);
+int damc_guided_sweep(const damc_denoiser_t* d, const float* xemb, const float* xemb_unc, float cond_w, float* zt,
+                      int batch, int n_steps, const float* temb_in, const float* coef, int with_noise,
+                      const float* noise, uint64_t seed, uint64_t chain_base, float* eps_log, int eps_log_steps,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ----------------------------------------------- Q training: denoiser loss step */
 /* The denoiser of Q.calculate_loss (workspace/src/diffusion_net.py:624-645, Diffusion_UnetA :463-533) as
