@@ -57,13 +57,23 @@ __device__ __forceinline__ Wf wmerge(Wf a, Wf b) {
 }
 
 // grid: (B * ceil(C/64), S); block 256 = 64 channels x 4 pixel lanes
-__global__ __launch_bounds__(256) void in_stats_kernel(const float* y, int B, int HW, int C, int S, float* part) {
+// PIVOT (the per-op norm calls): the statistics of y - K with K = the (sample, channel)'s first pixel, stored in
+// piv[b * C + c]; the partial means are then of the data's spread, not its offset, so neither the running mean of a
+// chain nor the difference of two partial means in wmerge rounds at |mean| (rstd 2.3e-6 from fp64 at |mean| = 1000 std
+// without it).  The consumer adds K back to the merged mean.  PIVOT = false keeps the absolute frame (piv unused)
+template <bool PIVOT>
+__device__ __forceinline__ void in_stats_body(const float* y, int B, int HW, int C, int S, float* part, float* piv) {
   const int cg = (C + 63) / 64;
   const int b = blockIdx.x / cg, c = (blockIdx.x % cg) * 64 + (threadIdx.x & 63);
   const int prow = threadIdx.x >> 6;
   const int s = blockIdx.y;
   const int p0 = (int)((long)HW * s / S), p1 = (int)((long)HW * (s + 1) / S);
   Wf w{0.f, 0.f, 0.f};
+  float K = 0.f;
+  if (PIVOT && c < C) {
+    K = y[(long)b * HW * C + c];
+    if (s == 0 && prow == 0) piv[(long)b * C + c] = K;
+  }
   if (c < C) {
     // four loads in flight, then their updates in pixel order (the same Welford chain as one at a time)
     int p = p0 + prow;
@@ -71,6 +81,10 @@ __global__ __launch_bounds__(256) void in_stats_kernel(const float* y, int B, in
       float v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = y[((long)b * HW + p + 4 * u) * C + c];
+      if (PIVOT) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = __fsub_rn(v[u], K);
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         w.n += 1.f;
@@ -80,7 +94,8 @@ __global__ __launch_bounds__(256) void in_stats_kernel(const float* y, int B, in
       }
     }
     for (; p < p1; p += 4) {
-      const float v = y[((long)b * HW + p) * C + c];
+      float v = y[((long)b * HW + p) * C + c];
+      if (PIVOT) v = __fsub_rn(v, K);
       w.n += 1.f;
       const float d = v - w.mean;
       w.mean += d / w.n;
@@ -99,10 +114,19 @@ __global__ __launch_bounds__(256) void in_stats_kernel(const float* y, int B, in
     o[2] = a.m2;
   }
 }
+__global__ __launch_bounds__(256) void in_stats_kernel(const float* y, int B, int HW, int C, int S, float* part) {
+  in_stats_body<false>(y, B, HW, C, S, part, nullptr);
+}
+__global__ __launch_bounds__(256) void in_stats_pivot_kernel(const float* y, int B, int HW, int C, int S, float* part,
+                                                             float* piv) {
+  in_stats_body<true>(y, B, HW, C, S, part, piv);
+}
 
-// grid: (B * ceil(C/64), P); merges the S partials of its 64 channels, then normalises its pixels
+// grid: (B * ceil(C/64), P); merges the S partials of its 64 channels (in_stats_pivot_kernel's, relative to piv),
+// then normalises its pixels
 __global__ __launch_bounds__(256) void in_apply_kernel(float* y, int B, int HW, int C, int S, const float* part,
-                                                       const float* gamma, const float* beta, float eps, float slope) {
+                                                       const float* piv, const float* gamma, const float* beta,
+                                                       float eps, float slope) {
   const int cg = (C + 63) / 64;
   const int b = blockIdx.x / cg, c = (blockIdx.x % cg) * 64 + (threadIdx.x & 63);
   const int prow = threadIdx.x >> 6;
@@ -114,21 +138,23 @@ __global__ __launch_bounds__(256) void in_apply_kernel(float* y, int B, int HW, 
       Wf a{pp[0], pp[1], pp[2]};
       for (int s = 1; s < S; ++s) a = wmerge(a, Wf{pp[3 * s], pp[3 * s + 1], pp[3 * s + 2]});
       const float var = a.m2 / a.n;  // biased, as InstanceNorm2d
-      const float rstd = 1.f / sqrtf(var + eps);
-      scale = rstd * gamma[c];
-      shift = beta[c] - a.mean * scale;
+      scale = 1.f / sqrtf(var + eps);
+      shift = __fadd_rn(piv[(long)b * C + c], a.mean);
     }
     sc[threadIdx.x] = scale;
     sh[threadIdx.x] = shift;
   }
   __syncthreads();
   if (c >= C) return;
-  const float scl = sc[threadIdx.x & 63], shf = sh[threadIdx.x & 63];
+  // a = ((y - mean) * rstd) * gamma + beta, InstanceNorm's own order and in_apply_train_kernel's bits: the fused
+  // y * (rstd * gamma) + (beta - mean * rstd * gamma) rounds the shift at |mean| * rstd * |gamma|, which is far above
+  // the output when |mean| >> std (a constant channel, hw = 1, or data riding on a large offset)
+  const float rstd = sc[threadIdx.x & 63], mean = sh[threadIdx.x & 63], g = gamma[c], bt = beta[c];
   const int P = gridDim.y;
   const int p0 = (int)((long)HW * blockIdx.y / P), p1 = (int)((long)HW * (blockIdx.y + 1) / P);
   for (int p = p0 + prow; p < p1; p += 4) {
     float* q = y + ((long)b * HW + p) * C + c;
-    const float v = fmaf(*q, scl, shf);
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(*q, mean), rstd), g), bt);
     *q = v > 0.f ? v : v * slope;
   }
 }
@@ -203,7 +229,8 @@ __global__ __launch_bounds__(256) void in_apply_f32_kernel(float* y, long n4, in
   *reinterpret_cast<f32x4*>(y + 4 * i) = v;
 }
 
-// the normalise + affine + LeakyReLU of in_apply_kernel (same fmaf), written as the next convolution's limbs (x3
+// the normalise + affine + LeakyReLU as one fmaf on in_merge_kernel's (scale, shift) (in_apply_kernel, the per-op call,
+// keeps InstanceNorm's own operation order instead), written as the next convolution's limbs (x3
 // octets) instead of fp32 in place: the limb engine reads nothing else.  One thread per (pixel, channel octet).
 // y32 != NULL: fp32 in place instead (y32 == y; every thread rewrites only the octet it read), for a next conv that
 // stages its input as fp32 (gemm.hip X3_F32A)
@@ -1228,7 +1255,7 @@ extern "C" int damc_conv2d_nhwc(const float* x, int B, int hin, int win, int cin
 }
 
 extern "C" size_t damc_instnorm_workspace_floats(int B, int hw, int c) {
-  return (size_t)B * c * in_splits(hw) * 3;
+  return (size_t)B * c * in_splits(hw) * 3 + (size_t)B * c;  // the partials, then the pivots (in_stats_pivot_kernel)
 }
 
 extern "C" int damc_instnorm_lrelu_nhwc(float* y, int B, int hw, int c, const float* gamma, const float* beta,
@@ -1238,9 +1265,11 @@ extern "C" int damc_instnorm_lrelu_nhwc(float* y, int B, int hw, int c, const fl
   const int S = in_splits(hw);
   const int cg = (c + 63) / 64;
   ProfScope ps("instnorm", 0.0, s);
-  hipLaunchKernelGGL(in_stats_kernel, dim3(B * cg, S), dim3(256), 0, s, y, B, hw, c, S, ws);
+  float* piv = ws + (size_t)B * c * S * 3;
+  hipLaunchKernelGGL(in_stats_pivot_kernel, dim3(B * cg, S), dim3(256), 0, s, (const float*)y, B, hw, c, S, ws, piv);
   const int P = std::max(1, std::min(64, hw / 256));
-  hipLaunchKernelGGL(in_apply_kernel, dim3(B * cg, P), dim3(256), 0, s, y, B, hw, c, S, ws, gamma, beta, eps, slope);
+  hipLaunchKernelGGL(in_apply_kernel, dim3(B * cg, P), dim3(256), 0, s, y, B, hw, c, S, ws, (const float*)piv, gamma,
+                     beta, eps, slope);
   return (int)hipGetLastError();
 }
 
@@ -1253,9 +1282,9 @@ extern "C" int damc_instnorm_lrelu_nhwc(float* y, int B, int hw, int c, const fl
 namespace {
 
 __global__ __launch_bounds__(256) void in_apply_train_kernel(const float* y, int B, int HW, int C, int S,
-                                                             const float* part, const float* gamma,
-                                                             const float* beta, float eps, float slope, float* h,
-                                                             float* stats) {
+                                                             const float* part, const float* piv,
+                                                             const float* gamma, const float* beta, float eps,
+                                                             float slope, float* h, float* stats) {
   const int cg = (C + 63) / 64;
   const int b = blockIdx.x / cg, c = (blockIdx.x % cg) * 64 + (threadIdx.x & 63);
   const int prow = threadIdx.x >> 6;
@@ -1269,9 +1298,9 @@ __global__ __launch_bounds__(256) void in_apply_train_kernel(const float* y, int
       const float var = a.m2 / a.n;
       const float rstd = 1.f / sqrtf(var + eps);
       scale = rstd;
-      shift = a.mean;
+      shift = __fadd_rn(piv[(long)b * C + c], a.mean);
       if (blockIdx.y == 0) {
-        stats[((long)b * C + c) * 2] = a.mean;
+        stats[((long)b * C + c) * 2] = shift;
         stats[((long)b * C + c) * 2 + 1] = rstd;
       }
     }
@@ -1370,10 +1399,11 @@ extern "C" int damc_instnorm_lrelu_train_nhwc(const float* y, int B, int hw, int
   const int S = in_splits(hw);
   const int cg = (c + 63) / 64;
   ProfScope ps("instnorm", 0.0, s);
-  hipLaunchKernelGGL(in_stats_kernel, dim3(B * cg, S), dim3(256), 0, s, y, B, hw, c, S, ws);
+  float* piv = ws + (size_t)B * c * S * 3;
+  hipLaunchKernelGGL(in_stats_pivot_kernel, dim3(B * cg, S), dim3(256), 0, s, y, B, hw, c, S, ws, piv);
   const int P = std::max(1, std::min(64, hw / 256));
-  hipLaunchKernelGGL(in_apply_train_kernel, dim3(B * cg, P), dim3(256), 0, s, y, B, hw, c, S, ws, gamma, beta, eps,
-                     slope, h, stats);
+  hipLaunchKernelGGL(in_apply_train_kernel, dim3(B * cg, P), dim3(256), 0, s, y, B, hw, c, S, (const float*)ws,
+                     (const float*)piv, gamma, beta, eps, slope, h, stats);
   return (int)hipGetLastError();
 }
 

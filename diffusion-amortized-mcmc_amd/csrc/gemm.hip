@@ -3397,6 +3397,12 @@ extern "C" unsigned long long damc_x3_tapshare_launches(void) {
 
 extern "C" int damc_gemm(const float* a, int lda, const float* b, int ldb, const float* bias, float* c, int ldc,
                          int m, int n, int k, int act, float slope, void* stream) {
+  if (!a || !b || !c || act < DAMC_ACT_NONE || act > DAMC_ACT_RELU) return DAMC_ERR_ARG;
+  if (lda < k || ldb < n || ldc < n) return DAMC_ERR_ARG;
+  if (act == DAMC_ACT_RELU) {  // the epilogue's act_apply has no ReLU of its own: LeakyReLU with slope 0
+    act = DAMC_ACT_LRELU;
+    slope = 0.f;
+  }
   damc::GemmArgs g;
   g.A = a;
   g.lda = lda;

@@ -196,7 +196,9 @@ int damc_conv2d_nhwc(const float* x, int batch, int hin, int win, int cin, const
  * (Cout, k,k,Cin) for the K-major engine when Cin % 32 == 0, else (k,k,Cin,Cout) */
 int damc_pack_conv2d(const float* w_torch, int cout, int cin, int k, float* w_packed, void* stream);
 /* InstanceNorm2d(affine, eps) + LeakyReLU(slope), in place on NHWC (Welford partials merged with
- * Chan's formula); workspace: damc_instnorm_workspace_floats() floats */
+ * Chan's formula, taken relative to each (sample, channel)'s first pixel so that a large common offset costs no
+ * accuracy; each element as ((y - mean) * rstd) * gamma + beta, the bits of the training call's h);
+ * workspace: damc_instnorm_workspace_floats() floats (the partials and one pivot per (sample, channel)) */
 size_t damc_instnorm_workspace_floats(int batch, int hw, int c);
 int damc_instnorm_lrelu_nhwc(float* y, int batch, int hw, int c, const float* gamma, const float* beta, float eps,
                              float slope, float* workspace, void* stream);
@@ -313,7 +315,10 @@ int damc_encoder_train_backward(const damc_encoder_t* enc, const float* saved, c
                                 const damc_encoder_grads_t* grads, void* workspace, size_t workspace_bytes,
                                 void* stream);
 
-/* Dense fp32 MFMA GEMM: C(M,N) = act(A(M,K) · B(K,N) + bias) with B row-major (K,N) */
+/* Dense fp32 MFMA GEMM: C(M,N) = act(A(M,K) · B(K,N) + bias) with B row-major (K,N); bias (N) or NULL; act any
+ * DAMC_ACT_* (slope: DAMC_ACT_LRELU's), any other value DAMC_ERR_ARG, as lda < k, ldb < n or ldc < n.  Any m, n, k >= 1
+ * and any 4-B aligned operands: K % 4, lda % 4 or a 16-B misaligned A (N % 4, ldb % 4 or B likewise) take scalar loads.
+ * Only C[i * ldc + j], i < m, j < n is written. */
 int damc_gemm(const float* a, int lda, const float* b, int ldb, const float* bias, float* c, int ldc, int m,
               int n, int k, int act, float slope, void* stream);
 
