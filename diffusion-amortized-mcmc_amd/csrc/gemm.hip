@@ -1122,6 +1122,37 @@ __device__ __forceinline__ void proj16(const float* tile, int ts, int r0, int C,
   }
 }
 
+// proj16 in two parts, for a caller that has other work to put between them: proj16_load_w takes this lane's weight
+// fragments of a chunk of cw <= PROJ_CHUNK channels (proj16's b operands: row 16 t + m, k = 16 g + 4 q .. + 3; zero past
+// cw) to registers, proj16_w runs proj16's MFMA sequence per output on them -- so the weight loads overlap whatever
+// comes between instead of chaining through proj16's k loop, and the result is bitwise proj16's
+template <int NT, int G0 = 0, int G1 = PROJ_CHUNK / 16>
+__device__ __forceinline__ void proj16_load_w(const float* w, int ldw, int cw, f32x4 (&wb)[PROJ_CHUNK / 16][NT]) {
+  const int lane = threadIdx.x & 63, m = lane & 15, q = lane >> 4;
+#pragma unroll
+  for (int g = G0; g < G1; ++g)
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      wb[g][t] = 16 * g < cw ? *reinterpret_cast<const f32x4*>(w + (long)(16 * t + m) * ldw + 16 * g + 4 * q)
+                             : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+template <int NT>
+__device__ __forceinline__ void proj16_w(const float* tile, int ts, int r0, int cw, const f32x4 (&wb)[PROJ_CHUNK / 16][NT],
+                                         f32x4 (&acc)[NT]) {
+  const int lane = threadIdx.x & 63, m = lane & 15, q = lane >> 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int g = 0; g < PROJ_CHUNK / 16; ++g) {
+    if (16 * g >= cw) break;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(tile + (r0 + m) * ts + 16 * g + 4 * q);
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], wb[g][t][e], acc[t], 0, 0, 0);
+  }
+}
+
 // the projection alone: 128 pixels per workgroup (8 waves x 16 rows) staged in LDS with gemm_x3_kernel's WIDE tile
 // stride, then proj16 (NT = np / 16) per 128-channel chunk (PROJ_CHUNK): chunk j's chain goes to partial buffer j
 // (P + j npix np), and the gather adds the partials in order -- the chunking of the F32A tile's fused projection, whose
@@ -1568,15 +1599,26 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     // whole groups (x3_tapshare_shape), so only a group's last tile flushes.
     unsigned ts_ibase = 0;
     int ts_nv = 0, ts_pstr = 0;
+    // x3_tapshare_ok admits only grids whose Hq Wq divides 256, so Hq Wq and Wq are powers of two: a row's (image, y, x)
+    // by shifts
+    [[maybe_unused]] const int ts_lhw = TSHARE ? __builtin_ctz((unsigned)hwq) : 0,
+                               ts_lwq = TSHARE ? __builtin_ctz((unsigned)p.Wq) : 0;
     if constexpr (TSHARE) {
-      constexpr int NT = TS_NT;
       const int r0 = tid >> 3, mi = m0 + r0;
-      const unsigned b = mi / hwq, r = mi - b * hwq, qy = r / p.Wq, qx = r - qy * p.Wq;
+      const unsigned b = (unsigned)mi >> ts_lhw, r = mi & (hwq - 1), qy = r >> ts_lwq, qx = r & (p.Wq - 1);
       ts_ibase = ((b * p.Hin + qy * p.stride) * Win + qx * p.stride) * Cg * 4 + ((tid & 7) ^ ts_swz(r0)) * 16;
       ts_nv = min(4, max(0, (p.M - mi + 63) >> 6));
-      ts_pstr = ((64 % hwq == 0) ? (64 / hwq) * p.Hin * Win : (64 / p.Wq) * p.stride * Win) * Cg * 4;
-      for (int id = tid; id < NT * BM; id += 512) {
-        const int row = id & (BM - 1), pos = id >> 8, m = m0 + row;
+      ts_pstr = ((64 % hwq == 0) ? (64 >> ts_lhw) * p.Hin * Win : (64 >> ts_lwq) * p.stride * Win) * Cg * 4;
+    }
+    // the read table and the zero rows (round 14: built behind the issue of image 0's and B(0)'s DMA, which do not
+    // depend on them; a thread's row -- id & 255 at stride 512 -- and its (y, x) are the same for all its entries)
+    auto ts_table = [&]() {
+      const int row = tid & (BM - 1), m = m0 + row;
+      const int rr = m & (hwq - 1), y = rr >> ts_lwq, x = rr & (p.Wq - 1);
+      const int iy = y * p.stride - pad_y, ix = x * p.stride - pad_x;
+#pragma unroll
+      for (int k = 0; k < TS_NT / 2; ++k) {
+        const int pos = (tid >> 8) + 2 * k;
         int ky, kx, dlt;
         if constexpr (OM == O_PHASE) {
           ky = pos >> 1;
@@ -1588,14 +1630,14 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
           kx = tp & 3;
           dlt = ((jj >> 1) - 1 + (c >> 1)) * p.Wq + (jj & 1) - 1 + (c & 1);
         }
-        const int bb = m / hwq, rr = m - bb * hwq, y = rr / p.Wq, x = rr - y * p.Wq;
         const int R = row + dlt;
-        const bool live = m < p.M && (unsigned)(y * p.stride - pad_y + ky) < (unsigned)p.Hin &&
-                          (unsigned)(x * p.stride - pad_x + kx) < (unsigned)Win && (unsigned)R < (unsigned)BM;
-        reinterpret_cast<int*>(smem + TS_TOFF)[id] = (live ? R * X3_ROWB : TS_ZERO + (R & 3) * X3_ROWB) + x3_swz(R) * 16;
+        const bool live = m < p.M && (unsigned)(iy + ky) < (unsigned)p.Hin && (unsigned)(ix + kx) < (unsigned)Win &&
+                          (unsigned)R < (unsigned)BM;
+        reinterpret_cast<int*>(smem + TS_TOFF)[tid + 512 * k] =
+            (live ? R * X3_ROWB : TS_ZERO + (R & 3) * X3_ROWB) + x3_swz(R) * 16;
       }
       if (tid < 4 * X3_ROWB / 4) reinterpret_cast<float*>(smem + TS_ZERO)[tid] = 0.f;
-    }
+    };
     // piece j of local group G: global group gg = (slice, class) for the 4 x 4 conv (class c = taps of parity (c >> 1,
     // c & 1), reading the pixels of the opposite parity), slice for a ConvT phase
     auto dma_img = [&](int G, int j) {
@@ -1705,6 +1747,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
         for (int j = 0; j < 4; ++j) dma_img(0, j);
         dma_b(kbeg, 0);
       }
+      ts_table();
       __syncthreads();  // the table, the zero rows, the staged image 0, B(0)
       {
         f32x4 av0[2][2];
@@ -2054,6 +2097,162 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
   long* rowtab = reinterpret_cast<long*>(smem + BM * TS * 4);
   float* Cz = p.C;
   if ((OM == O_DENSE || OM == O_WGRAD) && Cz) Cz += (long)(KSPLIT ? zph : z) * p.c_zstride;
+  if constexpr (TSHARE) {
+    // ---- the tap-shared tile's own epilogue (round 14; the unsplit launch -- a row-major slab goes the common way
+    // below): the arithmetic per output of the common octet pass and of proj16, so every byte stays the per-tap
+    // kernel's, scheduled for a CU whose MFMA pipes stand idle until the next tile's K loop:
+    //  - the fused projection's weight fragments are loaded first (proj16_load_w), under the tile write and the octet
+    //    pass, and the P stores take the output pixel from a second row table (rowpix) instead of dividing
+    //    rowtab by ldc per stored value;
+    //  - both row tables come from shifts (the grid's Hq Wq and Wq are powers of two);
+    //  - a thread's octet column (id % 16 at stride 512) is the same in its 8 rows: its bias is loaded once.
+    // Measured and not kept: a thread owning (row, four consecutive octets) with the four
+    // sign bytes as one dword -- 1.2 % slower per step, also where only the sign bytes are stored.
+    if (!KSPLIT) {  // workgroup-uniform
+      static_assert(BM * TS * 4 + BM * 8 + BM * 4 <= SMEMB, "epilogue tile and row tables exceed the LDS");
+      int* rowpix = reinterpret_cast<int*>(smem + BM * TS * 4 + BM * 8);
+      auto ts_epilogue = [&](auto NT_) {  // NT: 16-column tiles of the fused projection, 0 without one
+        constexpr int NT = decltype(NT_)::value;
+        constexpr bool PROJ = NT > 0;
+        f32x4 wb[PROJ_CHUNK / 16][PROJ ? NT : 1];
+        const int cw = min(PROJ_CHUNK, p.N - n0);  // a chunk narrower than 128 channels: the dead columns are skipped
+        // 64 registers of them here, under the tile write and the octet pass (np = 32: all; np = 64: the first four
+        // channel groups, the other four behind the octet pass, whose own registers they would crowd out)
+        constexpr int GW = NT <= 2 ? PROJ_CHUNK / 16 : PROJ_CHUNK / 32;
+        if constexpr (PROJ) proj16_load_w<NT, 0, GW>(p.proj_w + n0, p.proj_ldw, cw, wb);
+        if (tid < BM) {  // gemm_row_offset by shifts, and its pixel
+          const int m = m0 + tid;
+          long pix = -1;
+          if (m < p.M) {
+            if constexpr (OM == O_PHASE) {
+              const int lhw = __builtin_ctz((unsigned)hwq), lwq = __builtin_ctz((unsigned)p.Wq);
+              const int b = m >> lhw, rr = m & (hwq - 1), qy = rr >> lwq, qx = rr & (p.Wq - 1);
+              pix = ((long)b * p.Hout + 2 * qy + py) * p.Wout + 2 * qx + px;
+            } else {
+              pix = m;
+            }
+          }
+          rowtab[tid] = pix < 0 ? -1L : pix * p.ldc;
+          if constexpr (PROJ) rowpix[tid] = (int)pix;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              tile[(wm * 64 + i * 16 + 4 * (lane >> 4) + r) * TS + wn * 64 + j * 16 + (lane & 15)] = acc16[i][j][r];
+        __syncthreads();
+        // one octet (8 channels from n0 + 8 oct of tile row `row`, output offset idx): the common octet pass's arithmetic
+        // and stores but the sign byte, which it returns; bb: the octet's bias, mbits: its LReLU' mask bits
+        auto octet8 = [&](int row, int oct, long idx, const float (&bb)[8], unsigned mbits) -> unsigned {
+          const f32x4 t0 = *reinterpret_cast<const f32x4*>(tile + row * TS + oct * 8);
+          const f32x4 t1 = *reinterpret_cast<const f32x4*>(tile + row * TS + oct * 8 + 4);
+          float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+          if (EPI == EPI_BIAS_ACT) {
+            if (p.bias) {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] += bb[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = act_apply(v[e], p.act, p.slope);
+          } else if (EPI == EPI_MASK) {
+            if (p.mask_sgn) {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] *= ((mbits >> e) & 1u) ? 1.f : p.mask_slope;
+            } else {
+              const f32x4 k0 = *reinterpret_cast<const f32x4*>(p.mask + idx);
+              const f32x4 k1 = *reinterpret_cast<const f32x4*>(p.mask + idx + 4);
+              const float kk[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] *= act_grad_from_out(kk[e], p.mask_act, p.mask_slope);
+            }
+          }
+          unsigned bits = 0;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) bits |= (v[e] > 0.f ? 1u : 0u) << e;
+          if (Cz && !p.proj_nostore) {
+            *reinterpret_cast<f32x4*>(Cz + idx) = f32x4{v[0], v[1], v[2], v[3]};
+            *reinterpret_cast<f32x4*>(Cz + idx + 4) = f32x4{v[4], v[5], v[6], v[7]};
+          }
+          if (p.C3) {
+            bf16x8 h, m, l;
+            split3_octet(v, h, m, l);
+            bf16x8* o = reinterpret_cast<bf16x8*>(p.C3 + 3 * idx);
+            o[0] = h;
+            o[1] = m;
+            o[2] = l;
+          }
+          if constexpr (PROJ) {  // the stored row back into the tile, for the projection
+            *reinterpret_cast<f32x4*>(tile + row * TS + oct * 8) = f32x4{v[0], v[1], v[2], v[3]};
+            *reinterpret_cast<f32x4*>(tile + row * TS + oct * 8 + 4) = f32x4{v[4], v[5], v[6], v[7]};
+          }
+          return bits;
+        };
+        {
+          float bb[8] = {};  // this thread's octet column is id % 16 = tid & 15 in all of its rows
+          if (EPI == EPI_BIAS_ACT && p.bias && n0 + (tid & 15) * 8 < p.N) {
+            const int n = n0 + (tid & 15) * 8;
+            const int nb = p.bias_mod < p.N ? n % p.bias_mod : n;
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.bias + nb);
+            const f32x4 b1 = *reinterpret_cast<const f32x4*>(p.bias + nb + 4);
+            bb[0] = b0.x, bb[1] = b0.y, bb[2] = b0.z, bb[3] = b0.w;
+            bb[4] = b1.x, bb[5] = b1.y, bb[6] = b1.z, bb[7] = b1.w;
+          }
+#pragma unroll 2
+          for (int it = 0; it < BM * BN / 8 / 512; ++it) {
+            const int id = tid + 512 * it, row = id / (BN / 8), oct = id % (BN / 8);
+            const int n = n0 + oct * 8;
+            const long rowoff = rowtab[row];
+            if (rowoff < 0 || n >= p.N) continue;
+            const long idx = rowoff + n;
+            const unsigned mb = (EPI == EPI_MASK && p.mask_sgn) ? p.mask_sgn[idx >> 3] : 0u;
+            const unsigned sg = octet8(row, oct, idx, bb, mb);
+            if (p.sgn) p.sgn[idx >> 3] = (unsigned char)sg;
+          }
+        }
+        if constexpr (PROJ) {
+          // the fused output-layer projection (GemmArgs::proj_out): this tile's channels n0 .. n0 + 127 are chunk
+          // n0 / 128, 8 waves x 32 rows (two 16-row groups each), P indexed by the output pixel
+          if constexpr (GW < PROJ_CHUNK / 16)
+            proj16_load_w<NT, GW, PROJ_CHUNK / 16>(p.proj_w + n0, p.proj_ldw, cw, wb);
+          __syncthreads();
+          const int m = lane & 15, q = lane >> 4;
+          // the tap-shared K loop has no register to carry this wave's row base across it: taken from the thread id anew
+          int ptid = tid;
+          asm volatile("" : "+v"(ptid));
+          float* Pc = p.proj_out + (n0 / PROJ_CHUNK) * p.proj_pstride;
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            const int r0 = (ptid >> 6) * 32 + g * 16;
+            // one row group at a time: scheduled across this point, the F32A ConvT forward (CIFAR B=128) measured
+            // 0.8 % slower
+            __builtin_amdgcn_sched_barrier(0);
+            f32x4 acc[PROJ ? NT : 1];
+            proj16_w<PROJ ? NT : 1>(tile, TS, r0, cw, wb, acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int pix = rowpix[r0 + 4 * q + r];
+#pragma unroll
+              for (int t = 0; t < NT; ++t)
+                if (pix >= 0) Pc[(long)pix * (16 * NT) + 16 * t + m] = acc[t][r];
+            }
+          }
+        }
+      };
+      if constexpr (OM == O_PHASE && EPI == EPI_BIAS_ACT) {
+        if (p.proj_out) {  // workgroup-uniform
+          if (p.proj_np == 32)
+            ts_epilogue(std::integral_constant<int, 2>{});
+          else
+            ts_epilogue(std::integral_constant<int, 4>{});
+          return;
+        }
+      }
+      ts_epilogue(std::integral_constant<int, 0>{});
+      return;
+    }
+  }
   // one (row, channel octet) of the tile through the epilogue (bias + act / LReLU' mask, sign bits, fp32, limbs)
   auto octet = [&](int row, int oct) {
     const int n = n0 + oct * 8;
@@ -2201,7 +2400,7 @@ __global__ __launch_bounds__(512, (V & X3_NARROW) ? 2 : 1) void gemm_x3_kernel(G
     }
     return;
   }
-  epilogue();
+  if constexpr (!TSHARE) epilogue();
   if constexpr (OM == O_DENSE && EPI == EPI_BIAS_ACT && !WIDE && !NARROW && BM == 256 && BN == 128) {
     // the encoder norm's statistics of this tile (GemmArgs::in_part): its 256 rows are one strip of one sample
     static_assert(BM * TS * 4 + BM * 8 + 1024 * 4 <= 2 * (BM + BN) * X3_ROWB, "statistics scratch exceeds the LDS");

@@ -1,6 +1,7 @@
 """Per-workgroup start / K-loop end of every limb-engine launch of one posterior step (damc_clock_probe stamps,
 100 MHz realtime; DAMC_CLOCK_REGIONS gives each launch its own slot region): where does a small-batch GEMM's time
-go?  usage: python tools/step_wg_probe.py [net:B ...]   (default svhn:64 cifar10:16; run through gpurun)"""
+go?  A launch with more workgroups than CUs is also listed per round (DAMC_PROBE_DUMP=PREFIX keeps the raw stamps).
+usage: python tools/step_wg_probe.py [net:B ...]   (default svhn:64 cifar10:16; needs the GPU)"""
 import os
 import sys
 
@@ -16,6 +17,7 @@ NETS = {"cifar10": ("_netG_cifar10", 128, 128, 32, 0.1), "svhn": ("_netG_svhn", 
         "celeba64": ("_netG_celeba64", 100, 128, 64, 0.1), "celebaHQ": ("_netG_celebaHQ", 128, 128, 256, 1.0)}
 R, SLOTS = int(os.environ["DAMC_CLOCK_REGIONS"]), 4096
 dev = torch.device("cuda:0")
+NCU = torch.cuda.get_device_properties(0).multi_processor_count
 L = _lib.lib()
 q = torch.tensor([0.0, 0.5, 1.0], dtype=torch.float64)
 for case in (sys.argv[1:] or ["svhn:64", "cifar10:16"]):
@@ -33,6 +35,9 @@ for case in (sys.argv[1:] or ["svhn:64", "cifar10:16"]):
     torch.cuda.synchronize()
     L.damc_clock_probe(None, 0)
     c = clk.view(R, SLOTS, 4).cpu().double()
+    if os.environ.get("DAMC_PROBE_DUMP"):  # the raw stamps (regions x slots x 4) as .npy, for analysis elsewhere
+        import numpy as np
+        np.save("%s_%s_B%d.npy" % (os.environ["DAMC_PROBE_DUMP"], net, B), clk.view(R, SLOTS, 4).cpu().numpy())
     live = [c[r][c[r][:, 1] > 0] for r in range(R)]
     t0 = min(float(v[:, 1].min()) for v in live if len(v))
     print("== %s B=%d: one posterior step's limb-engine launches (us from the first workgroup start; 100 MHz)" % (net, B))
@@ -46,5 +51,22 @@ for case in (sys.argv[1:] or ["svhn:64", "cifar10:16"]):
             r, len(v), [round(float(a), 1) for a in torch.quantile(st, q)],
             [round(float(a), 1) for a in torch.quantile(en, q)], [round(float(a), 1) for a in torch.quantile(du, q)],
             float(ghz)), flush=True)
+        # rounds of a launch with more workgroups than CUs (one 256 x 128 workgroup per CU): workgroups in start order,
+        # NCU per round; the k-th K-loop end of a round against the k-th start of the next is the time a CU spends
+        # between two K loops' stamps (epilogue, workgroup turnover; the next prologue sits inside its per-WG time)
+        if len(v) > NCU:
+            o = torch.argsort(st)
+            so, eo = st[o], en[o]
+            for k in range(0, len(v), NCU):
+                s_, e_ = so[k:k + NCU], torch.sort(eo[k:k + NCU]).values
+                line = "  round %d: start q0/50/100 %s  end %s  per-WG %s" % (
+                    k // NCU, [round(float(a), 1) for a in torch.quantile(s_, q)],
+                    [round(float(a), 1) for a in torch.quantile(e_, q)],
+                    [round(float(a), 1) for a in torch.quantile(eo[k:k + NCU] - s_, q)])
+                if k + NCU < len(v):
+                    nx = so[k + NCU:k + 2 * NCU]
+                    gap = nx - e_[:len(nx)]
+                    line += "  end -> next start %s" % [round(float(a), 1) for a in torch.quantile(gap, q)]
+                print(line, flush=True)
     del G, E, x, z
     torch.cuda.empty_cache()
