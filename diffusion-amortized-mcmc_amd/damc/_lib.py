@@ -132,6 +132,14 @@ class MlpGrads(ctypes.Structure):  # damc_mlp_grads_t
     _fields_ = [("w", ctypes.c_void_p * MLP_MAX_LAYERS), ("b", ctypes.c_void_p * MLP_MAX_LAYERS)]
 
 
+SPECNORM_MAX_LAYERS = 8
+
+
+class SpecNormLayer(ctypes.Structure):  # damc_specnorm_layer_t
+    _fields_ = [(k, ctypes.c_void_p) for k in ("w_orig", "u", "v", "w_hat", "sigma", "u_used", "v_used")] + [
+        ("a", ctypes.c_int), ("r", ctypes.c_int), ("k", ctypes.c_int), ("eps", ctypes.c_float)]
+
+
 class AdamHparams(ctypes.Structure):
     _fields_ = [("neg_step_size", ctypes.c_float), ("one_minus_beta1", ctypes.c_float), ("beta2", ctypes.c_float),
                 ("one_minus_beta2", ctypes.c_float), ("bc2_sqrt", ctypes.c_float), ("eps", ctypes.c_float),
@@ -244,6 +252,9 @@ _SIGS = {
     "damc_grad_norm_finish": (_I, [_P, _I, _F, _P, _P]),
     "damc_grad_scale": (_I, [_P, _I, _P, _I, _P, _P]),
     "damc_adam_step": (_I, [_P, _I, _P, _P, _P, _P, _I, ctypes.POINTER(AdamHparams), _P, _P]),
+    "damc_specnorm_workspace_bytes": (_SZ, [ctypes.POINTER(SpecNormLayer), _I]),
+    "damc_specnorm_forward": (_I, [ctypes.POINTER(SpecNormLayer), _I, _I, _P, _SZ, _P]),
+    "damc_specnorm_backward": (_I, [ctypes.POINTER(SpecNormLayer), _I, ctypes.POINTER(ctypes.c_void_p), _P, _SZ, _P]),
     "damc_fid_accumulate": (_I, [_P, _I, _I, _P, _P, _P]),
     "damc_fid_mean_cov": (_I, [_P, _P, ctypes.c_double, _I, _P, _P, _P]),
     "damc_prof_enable": (_I, [_I]),

@@ -62,6 +62,8 @@ def _live_weight(m):
     h = _sn_hook(m)
     if h is None:
         return m.weight
+    if getattr(_SN, "preset", False):  # the G update: damc.training.specnorm_apply has set this forward's weight
+        return getattr(m, h.name)
     if m.training:
         if not getattr(_SN, "on", False):
             raise NotImplementedError("spectral-norm layer in train mode outside spectral_norm_step: its forward "
@@ -100,6 +102,37 @@ def spectral_norm_step(layers):
         yield
     finally:
         _SN.on = prev
+
+
+@contextlib.contextmanager
+def spectral_norm_preset(on=True):
+    """Inside the block the plans pack the weight already set on each spectral-norm module, in either mode: the
+    training forwards (damc.training.specnorm_apply) compute it on libdamc with the hook's semantics -- power iteration
+    in train mode only, u and v in place -- and set it as the hook does, so nothing is recomputed here."""
+    prev = getattr(_SN, "preset", False)
+    _SN.preset = bool(on)
+    try:
+        yield
+    finally:
+        _SN.preset = prev
+
+
+def sn_layers(modules):
+    """(module, SpectralNorm hook) of every layer with nn.utils.spectral_norm among modules, in either mode."""
+    return [(m, h) for m, h in ((m, _sn_hook(m)) for m in modules) if h is not None]
+
+
+def specnorm_view(shape, dim):
+    """(A, R, K) of the in-place 3-d view [A][R][K] of a weight_orig of this shape whose matrix -- the hook's
+    reshape_weight_to_matrix: dim moved to the front, the rest flattened in order -- has the middle index as its row
+    and a * K + k as its column.  Linear (dim 0): (1, out, in); ConvTranspose2d (dim 1): (cin, cout, kh * kw)."""
+    shape = tuple(int(s) for s in shape)
+    a = k = 1
+    for s in shape[:dim]:
+        a *= s
+    for s in shape[dim + 1:]:
+        k *= s
+    return a, shape[dim], k
 
 
 class GeneratorPlan:
@@ -182,10 +215,11 @@ class GeneratorPlan:
             d.w_bwd = wb.data_ptr() if bwd.value else None
         self.desc = desc
 
-    def refresh(self, device, engine=None):
+    def refresh(self, device, engine=None, weights=None):
         """(Re)pack the live parameters; returns a per-call copy of the ctypes descriptor (so threads asking for
         different engines never share one).  engine: _lib.ENGINE_* for every layer (default:
-        _lib.current_engine() of the calling thread)."""
+        _lib.current_engine() of the calling thread).  weights: one tensor per layer to pack instead of the modules'
+        live ones (a training backward packing its forward's saved weights again)."""
         device = torch.device(device)
         engine = _lib.current_engine() if engine is None else int(engine)
         if device.type != "cuda":
@@ -196,7 +230,7 @@ class GeneratorPlan:
         stream = _lib.stream_ptr(device)
         self._keep = []
         for i, m in enumerate(self.modules):
-            w = _live_weight(m).detach()
+            w = (_live_weight(m) if weights is None else weights[i]).detach()
             if w.device != device or w.dtype != torch.float32 or not w.is_contiguous():
                 w = w.to(device=device, dtype=torch.float32).contiguous()
                 self._keep.append(w)

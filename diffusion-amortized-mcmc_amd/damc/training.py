@@ -13,7 +13,9 @@ keeping the activations and LReLU' sign bits in a per-call workspace) and whose 
 ``damc_generator_train_backward`` (dL/dx_hat -> every layer's dL/dW, dL/db and optionally dL/dz, with
 the k4 s2 p1 / first-layer weight gradients on the limb engine).  The loss, ``clip_grad_norm_`` and the
 optimiser stay the caller's PyTorch code, unchanged.  Without grad (``torch.no_grad()``, or nothing
-requiring grad) it is the plain HIP forward.
+requiring grad) it is the plain HIP forward.  A spectral-norm generator (``use_spc_norm=True``) takes the
+same Function on its normalised weights, computed by ``damc_specnorm_forward`` with the hook's semantics;
+``damc_specnorm_backward`` carries the gradient on to ``weight_orig``.
 """
 import contextlib
 import ctypes
@@ -24,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .plans import generator_plan
+from .plans import _sn_hook, generator_plan, sn_layers, specnorm_view, spectral_norm_preset
 
 # The drop-in modules route their ROCm training forward/backward here while ENABLED; `stock_pytorch()`
 # turns that off explicitly (benchmark comparisons against the reference's own PyTorch path only).
@@ -51,6 +53,15 @@ def _params_of(plan):
     return out
 
 
+def _saved_weights(plan, saved):
+    """The weight of every layer among a forward's saved parameters (the order of _params_of)."""
+    out, k = [], 0
+    for m in plan.modules:
+        out.append(saved[k])
+        k += 2 if m.bias is not None else 1
+    return out
+
+
 class _GeneratorTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, plan, *params):
@@ -68,6 +79,11 @@ class _GeneratorTrainFn(torch.autograd.Function):
         check(L.damc_generator_train_forward(ctypes.byref(desc), ptr(zc), B, ptr(xh), ptr(ws), nbytes,
                                              _lib.stream_ptr(dev)), "damc_generator_train_forward")
         ctx.plan, ctx.ws, ctx.nbytes = plan, ws, nbytes
+        # spectral-norm layers: every forward packs its own normalised weights (u, v advance in train mode), so a
+        # second G(z) before this one's backward leaves other weights in the plan's buffers; the backward notices by
+        # the pack count and packs the saved ones again
+        plan.packs = getattr(plan, "packs", 0) + 1
+        ctx.packs = plan.packs if sn_layers(plan.modules) else None
         # refresh returned a private descriptor: a later refresh (other engine, other thread) cannot change what
         # the backward runs on — it has to be the engine that filled this workspace
         ctx.desc = desc
@@ -88,7 +104,10 @@ class _GeneratorTrainFn(torch.autograd.Function):
         # values); re-pack only if the plan re-allocated them (device change)
         desc = ctx.desc
         if plan.buffers is not ctx.keep[0]:  # buffers re-allocated (device change): re-pack, same engine
-            desc = plan.refresh(dev, engine=desc.layers[0].engine)
+            desc = plan.refresh(dev, engine=desc.layers[0].engine, weights=_saved_weights(plan, ctx.saved_tensors[2:]))
+        elif ctx.packs is not None and ctx.packs != plan.packs:
+            desc = plan.refresh(dev, engine=desc.layers[0].engine, weights=_saved_weights(plan, ctx.saved_tensors[2:]))
+            plan.packs += 1
         gx = gx.to(torch.float32).contiguous()
         grads = _lib.GeneratorGrads()
         outs = []
@@ -105,8 +124,113 @@ class _GeneratorTrainFn(torch.autograd.Function):
         return (gz, None, *outs)
 
 
+# ------------------------------------------------------------------------------------ spectral norm
+# nn.utils.spectral_norm's forward pre-hook (torch/nn/utils/spectral_norm.py SpectralNorm.compute_weight; the
+# reference's sn, diffusion_net.py:8-16) for every spectral-norm layer of a net in one grouped call each way
+# (damc_specnorm_forward / _backward, csrc/specnorm.hip) instead of ~12 small PyTorch ops per layer: the power
+# iteration in train mode only, u and v written in place into the module's buffers, the normalised weight set on the
+# module as the hook sets it, and dL/dW_hat -> dL/dweight_orig with u, v constants of the graph.
+
+def _specnorm_spec(layers):
+    """([(A, R, K) per layer], power iterations of this forward) for [(module, SpectralNorm hook)], or None where the
+    library does not take them: more than 8 layers, layers in different modes, a weight / u / v that is not a
+    contiguous fp32 ROCm tensor."""
+    if not layers or len(layers) > _lib.SPECNORM_MAX_LAYERS:
+        return None
+    modes = {(bool(m.training), int(h.n_power_iterations)) for m, h in layers}
+    if len(modes) != 1:
+        return None
+    views = []
+    for m, h in layers:
+        w, u, v = (getattr(m, h.name + s, None) for s in ("_orig", "_u", "_v"))
+        if w is None or u is None or v is None or not 0 <= h.dim < w.dim():
+            return None
+        if any(t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" or t.device != w.device
+               for t in (w, u, v)):
+            return None
+        a, r, k = specnorm_view(w.shape, h.dim)
+        if min(a, r, k) < 1 or u.numel() != r or v.numel() != a * k:
+            return None
+        views.append((a, r, k))
+    train, npi = modes.pop()
+    return views, (npi if train else 0)
+
+
+class _SpecNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, spec, *w_origs):
+        layers, views, npi = spec
+        dev = w_origs[0].device
+        n = len(layers)
+        # this forward's sigma, u, v (the hook's clone()s): a later forward advances the module's u, v, not these
+        sizes = []
+        for a, r, k in views:
+            sizes += [4, r + (-r) % 4, a * k + (-a * k) % 4]
+        parts = torch.empty(sum(sizes), dtype=torch.float32, device=dev).split(sizes)
+        whats = [torch.empty_like(w) for w in w_origs]
+        tab = (_lib.SpecNormLayer * n)()
+        for i, ((m, h), (a, r, k), w) in enumerate(zip(layers, views, w_origs)):
+            t = tab[i]
+            t.w_orig, t.u, t.v = w.data_ptr(), getattr(m, h.name + "_u").data_ptr(), getattr(m, h.name + "_v").data_ptr()
+            t.w_hat, t.sigma, t.u_used, t.v_used = (whats[i].data_ptr(), parts[3 * i].data_ptr(),
+                                                    parts[3 * i + 1].data_ptr(), parts[3 * i + 2].data_ptr())
+            t.a, t.r, t.k, t.eps = a, r, k, float(h.eps)
+        L = _lib.lib()
+        nb = int(L.damc_specnorm_workspace_bytes(tab, n))
+        if nb == 0:
+            raise _lib.DamcError("spectral-norm layer table not taken by damc_specnorm_forward")
+        check(L.damc_specnorm_forward(tab, n, int(npi), ptr(_scratch("specnorm", dev, nb)), nb, _lib.stream_ptr(dev)),
+              "damc_specnorm_forward")
+        ctx.tab, ctx.n, ctx.nb, ctx.keep = tab, n, nb, parts
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*whats)
+        return tuple(whats)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        whats = ctx.saved_tensors
+        dev = whats[0].device
+        garr = (ctypes.c_void_p * ctx.n)()
+        outs = []
+        for i, g in enumerate(gs):
+            if g is None or not ctx.needs_input_grad[1 + i]:
+                outs.append(None)
+                continue
+            g32 = g.to(torch.float32).contiguous()
+            if g32 is g:  # the library works in place; autograd's tensor may have other readers
+                g32 = g.clone()
+            outs.append(g32)
+            garr[i] = g32.data_ptr()
+        if any(o is not None for o in outs):
+            check(_lib.lib().damc_specnorm_backward(ctx.tab, ctx.n, garr, ptr(_scratch("specnorm_bwd", dev, ctx.nb)),
+                                                    ctx.nb, _lib.stream_ptr(dev)), "damc_specnorm_backward")
+        return (None, *outs)
+
+
+def specnorm_apply(layers):
+    """This forward's normalised weight of every [(module, SpectralNorm hook)] layer on libdamc, set on the modules as
+    the hook sets it; the list of them, or None where the library does not take the layers (nothing is changed then)."""
+    spec = _specnorm_spec(layers)
+    if spec is None:
+        return None
+    w_origs = [getattr(m, h.name + "_orig") for m, h in layers]
+    whats = _SpecNormFn.apply((layers,) + spec, *w_origs)
+    for (m, h), w in zip(layers, whats):
+        setattr(m, h.name, w)
+    return list(whats)
+
+
+def _foreign_reparam(G):
+    seq = G.gen if hasattr(G, "gen") else G.net
+    return any(isinstance(m, (torch.nn.ConvTranspose2d, torch.nn.Linear)) and "weight" not in m._parameters
+               and _sn_hook(m) is None for m in seq)
+
+
 def generator_apply(G, z):
-    """x_hat = G(z) on the HIP path, differentiable w.r.t. z and G's parameters."""
+    """x_hat = G(z) on the HIP path, differentiable w.r.t. z and G's parameters.  None for a generator whose
+    reparametrised weights the library does not take (the caller then runs the stock modules)."""
+    if _foreign_reparam(G):
+        return None
     plan = generator_plan(G)
     if z.dim() == 4:
         z = z.reshape(z.shape[0], -1)
@@ -114,6 +238,19 @@ def generator_apply(G, z):
         raise _lib.DamcError("z of shape %s for a generator with nz=%d" % (tuple(z.shape), plan.nz))
     if z.device.type != "cuda":
         raise _lib.DamcError("the HIP generator path needs ROCm tensors (got %s)" % z.device)
+    sn = sn_layers(plan.modules)
+    if sn:
+        # spectral-norm generator (use_spc_norm=True): the hook's work on libdamc, then the same training Function on
+        # the normalised weights; autograd composes its dL/dW_hat with damc_specnorm_backward onto weight_orig
+        leaves = [p for m in plan.modules for p in m.parameters(recurse=False)]
+        if torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in leaves)):
+            if specnorm_apply(sn) is None:
+                return None
+            with spectral_norm_preset():
+                return _GeneratorTrainFn.apply(z, plan, *[p for _, _, p in _params_of(plan)])
+        from .langevin import generator_forward
+
+        return generator_forward(z.to(torch.float32).contiguous(), G)
     params = [p for _, _, p in _params_of(plan)]
     if torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in params)):
         return _GeneratorTrainFn.apply(z, plan, *params)
@@ -351,16 +488,26 @@ def q_loss(eps, eps_pred):
 # ----------------------------------------------------------------------------------------- E update
 # e_pos, e_neg = E(zk_pos), E(zk_neg); (e_pos.mean() - e_neg.mean()).backward() (train_gen_recon.py:233-241) with
 # _netE's forward and backward on libdamc (damc_ebm_train_*): three small-GEMM launches forward, two elementwise and
-# two grouped launches backward, instead of ~25 PyTorch ops.  Shapes the C side does not take (batch or widths not a
-# multiple of 4, nez != 1, spectral norm, non-fp32 or misaligned tensors) keep the stock PyTorch modules.
+# two grouped launches backward, instead of ~25 PyTorch ops.  _netE(e_sn=True) takes the same kernels on this forward's
+# spectral-normalised weights (specnorm_apply above: five grouped launches forward, three backward, for the three
+# layers together).  Shapes the C side does not take (batch or widths not a multiple of 4, nez != 1, a
+# reparametrisation other than nn.utils.spectral_norm's, non-fp32 or misaligned tensors) keep the stock PyTorch modules.
 
-def _ebm_layers(E):
+def _ebm_layers(E, spectral=False):
+    """(the three Linears, slope) of a _netE the E-update kernels take, or None.  spectral: the second route, for
+    _netE(e_sn=True) -- the same topology with every Linear under nn.utils.spectral_norm (ebm_apply then points the
+    descriptor at the normalised weights); the plain route refuses any reparametrised layer."""
     mods = list(E.ebm)
     lins = [m for m in mods if isinstance(m, torch.nn.Linear)]
     acts = [m for m in mods if isinstance(m, torch.nn.LeakyReLU)]
     if len(mods) != 5 or len(lins) != 3 or len(acts) != 2 or mods[0] is not lins[0] or mods[2] is not lins[1]:
         return None
-    if any(hasattr(m, "weight_orig") for m in lins) or acts[0].negative_slope != acts[1].negative_slope:
+    if acts[0].negative_slope != acts[1].negative_slope:
+        return None
+    if spectral:
+        if any(_sn_hook(m) is None or not hasattr(m, "weight_orig") for m in lins):
+            return None
+    elif any("weight" not in m._parameters for m in lins):  # any reparametrised layer
         return None
     # the backward (ebm.hip et_dh2_kernel / et_mask_kernel) reads LReLU' from the sign of the post-activation, which is
     # the pre-activation's sign only for a slope >= 0 (ADVICE r5): other slopes keep the stock modules
@@ -415,11 +562,19 @@ class _EbmTrainFn(torch.autograd.Function):
 def ebm_apply(E, z):
     """E(z).squeeze() on libdamc with grad (the E update), or None where the C side does not take the module / input
     (the caller then runs the stock modules)."""
-    lay = _ebm_layers(E)
-    if lay is None or z.dim() != 2 or z.dtype != torch.float32 or z.shape[0] % 4:
+    lay, sn = _ebm_layers(E), None
+    if lay is None:
+        lay = _ebm_layers(E, spectral=True)  # _netE(e_sn=True)
+        if lay is None:
+            return None
+        sn = sn_layers(lay[0])
+        if _specnorm_spec(sn) is None:
+            return None
+    if z.dim() != 2 or z.dtype != torch.float32 or z.shape[0] % 4:
         return None
     lins, slope = lay
-    params = [t for m in lins for t in (m.weight, m.bias)]
+    # every eligibility test runs on weight_orig first: the spectral-norm forward advances u and v
+    params = [t for m in lins for t in (m.weight_orig if sn else m.weight, m.bias)]
     if any(p.dtype != torch.float32 or not p.is_contiguous() or p.data_ptr() % 16 for p in params):
         return None
     z = z.contiguous()
@@ -430,6 +585,11 @@ def ebm_apply(E, z):
     d.w1, d.b1, d.w2, d.b2, d.w3, d.b3 = [p.data_ptr() for p in params]
     if int(_lib.lib().damc_ebm_train_workspace_bytes(ctypes.byref(d), z.shape[0])) == 0:
         return None
+    if sn:
+        # this forward's normalised weights, each forward its own (e_pos, e_neg = E(a), E(b) before one backward):
+        # the descriptor and the saved tensors point at them, and their gradients flow on to weight_orig
+        params[0::2] = specnorm_apply(sn)
+        d.w1, d.w2, d.w3 = [p.data_ptr() for p in params[0::2]]
     return _EbmTrainFn.apply(z, d, slope, *params)
 
 
@@ -642,7 +802,7 @@ def encoder_train_supported(enc, x):
 # kernels are stream-ordered, so one buffer per purpose serves every stage and every call on a stream (round 5: ~20
 # torch.empty calls per Q update, ~0.1 ms of host time)
 _ENC_SCRATCH = {k: _lib.WorkspaceCache() for k in ("w3", "conv", "in", "in_bwd", "conv_bwd", "ebm_bwd", "enc_train", "prior_emb_bwd",
-                                                   "mlp_bwd")}
+                                                   "mlp_bwd", "specnorm", "specnorm_bwd")}
 
 
 def _scratch(key, device, nbytes):

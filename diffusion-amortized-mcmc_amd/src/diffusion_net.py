@@ -5,9 +5,11 @@ reference checkpoints load unchanged (workspace/train_gen_recon.py:284-294).  Th
 built from compact spec tables.  The hot path — Langevin sampling and the amortizer's
 reverse sweep — runs on the HIP kernels: ``_netQ_U.forward`` dispatches to
 ``damc.amortizer`` and ``src.MCMC`` to ``damc.langevin``.  ``_netG_*.forward`` on ROCm
-tensors runs on libdamc too, with a HIP backward for the G update (``damc.training``).
-``forward`` of E / encoders / denoiser stays stock PyTorch (their training updates are
-outside the hot path).
+tensors runs on libdamc too, with a HIP backward for the G update (``damc.training``), and so
+do the training forwards of E, the encoders and the denoiser for the shapes the library takes.
+Spectral-norm nets (``use_spc_norm=True`` generators, ``e_sn=True`` EBMs) stay on the library in
+their G and E updates as well: the hook's work is one grouped call each way
+(``damc.training.specnorm_apply``).
 """
 import math
 
@@ -57,13 +59,16 @@ class _GeneratorBase(nn.Module):
     def forward(self, z):
         # ROCm tensors run on libdamc: the forward, and under autograd the training backward
         # (damc.training: dL/dW, dL/db, dL/dz for the G update, train_gen_recon.py:222-231).
-        # Spectral-norm generators (use_spc_norm=True, default False) run their forward on the stock layers (the
-        # Langevin chains, gen_samples and the sweeps take them on libdamc in eval mode: damc.plans._live_weight).
-        if z.is_cuda and not self._spc:
+        # Spectral-norm generators (use_spc_norm=True, default False) too: the hook's power iteration, sigma and
+        # normalised weights by damc_specnorm_forward, the gradient onto weight_orig by damc_specnorm_backward.
+        # None: a reparametrisation or tensor layout the library does not take, then the stock layers.
+        if z.is_cuda:
             from damc import training
 
             if training.ENABLED:
-                return training.generator_apply(self, z)
+                x_hat = training.generator_apply(self, z)
+                if x_hat is not None:
+                    return x_hat
         return self.gen(z.reshape(z.shape[0], self.nz, 1, 1))
 
 

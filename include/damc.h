@@ -537,6 +537,34 @@ int damc_prior_emb_train_backward(const damc_prior_emb_t* e, const float* noise,
                                   int batch, const damc_prior_emb_grads_t* grads, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------ spectral norm of a net's layers (G and E updates with use_spc_norm / e_sn)
+ * One forward of torch.nn.utils.spectral_norm's SpectralNorm.compute_weight (torch/nn/utils/spectral_norm.py; the
+ * reference's sn, diffusion_net.py:8-16) and its gradient, for up to DAMC_SPECNORM_MAX_LAYERS layers in grouped
+ * launches (one grid covers every layer).  w_orig is read in place in its PyTorch layout as a 3-d view [a][r][k] whose
+ * matrix row is the middle index and whose column is a_i * k + k_i: Linear(out, in) is [1][out][in] (the hook's
+ * dim = 0), ConvTranspose2d(cin, cout, kh, kw) is [cin][cout][kh * kw] (dim = 1); no permuted copy is made.
+ * Forward, per power iteration: v <- W^T u / max(|W^T u|, eps), u <- W v / max(|W v|, eps), written in place into
+ * the module's own u (r) and v (a * k) buffers; then sigma = u^T (W v) and w_hat = w_orig / sigma (an IEEE divide) in
+ * w_orig's layout, plus sigma (1) and the copies u_used (r), v_used (a * k) the backward reads.  Backward: g[i] holds
+ * dL/dw_hat in that layout and is overwritten with dL/dw_orig = (g - <g, w_hat> u_used v_used^T) / sigma (u, v are
+ * constants of the graph, as in the hook); it reads w_hat, sigma, u_used, v_used only, and a NULL g[i] skips layer i.
+ * Every reduction is a fixed-order two-stage sum through the workspace (no atomics; scalars finish in fp64): results
+ * are bitwise repeatable.  16-byte accesses when k % 4 == 0 and the layer's pointers are 16-B aligned, scalar ones
+ * otherwise.  workspace_bytes: 0 when the table is not taken (n < 1, n > 8, a NULL layer pointer, an extent < 1). */
+#define DAMC_SPECNORM_MAX_LAYERS 8
+typedef struct {
+  const float* w_orig;
+  float *u, *v;                           /* the module's buffers, updated in place */
+  float *w_hat, *sigma, *u_used, *v_used; /* per-forward outputs, the backward's inputs */
+  int a, r, k;
+  float eps;
+} damc_specnorm_layer_t;
+size_t damc_specnorm_workspace_bytes(const damc_specnorm_layer_t* layers, int n);
+int damc_specnorm_forward(const damc_specnorm_layer_t* layers, int n, int power_iterations, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int damc_specnorm_backward(const damc_specnorm_layer_t* layers, int n, float* const* g, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------------------------- optimiser steps
  * Replaces the G/E/Q updates' torch.nn.utils.clip_grad_norm_ + optim.Adam / optim.AdamW.step()
  * (train_gen_recon.py:155-157, 219-231, 240-241) by multi-tensor kernels.  A launch covers up to
