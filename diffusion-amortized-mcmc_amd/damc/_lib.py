@@ -201,6 +201,11 @@ _SIGS = {
     "damc_ebm_energy_grad": (_I, [ctypes.POINTER(Ebm), _P, _I, _P, _P, _P]),
     "damc_z_update": (_I, [_P, _P, _I, _I, _D, _I, _P, _U64, _U64, _U64, _P]),
     "damc_philox_normal": (_I, [_P, _I, _I, _I, _U64, _U64, _U64, ctypes.c_uint32, _P]),
+    "damc_recon_rows_workspace_bytes": (_SZ, [_I, ctypes.c_long]),
+    "damc_recon_rows": (_I, [_P, _P, _I, ctypes.c_long, _P, _P, _SZ, _P]),
+    "damc_posterior_energy_workspace_bytes": (_SZ, [ctypes.POINTER(Generator), _I]),
+    "damc_posterior_energy": (_I, [ctypes.POINTER(Generator), ctypes.POINTER(Ebm), _P, _P, _I, _F, _P, _P, _P, _P, _SZ,
+                                   _P]),
     "damc_conv2d_workspace_floats": (_SZ, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "damc_conv2d_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "damc_pack_conv2d": (_I, [_P, _I, _I, _I, _P, _P]),

@@ -7,7 +7,8 @@ start: Philox noise is keyed by the global chain index, so the union of the shar
 1-GPU result.  The only collectives are the final reductions below (``all_reduce(SUM)`` over
 RCCL/xGMI for backend "nccl", or gloo in the CPU tests):
   * reconstruction MSE (eval_gen_recon.py:177-212): [sum of per-sample MSE, count];
-  * FID sufficient statistics (MCMC.py:130-176 feed pfw.fid): [sum f, sum f f^T, n] in fp64.
+  * FID sufficient statistics (MCMC.py:130-176 feed pfw.fid): [sum f, sum f f^T, n] in fp64;
+and, for the anomaly score, which is not a sum, one ``all_gather`` of fixed-size slices (``all_gather_shards``).
 """
 import torch
 
@@ -130,3 +131,74 @@ def sharded_recon_mse(Q, G, E, batches, g_l_steps=10, g_llhd_sigma=0.1, g_l_step
     if meter is None:
         meter = ReconMSE(torch.device("cuda"))
     return meter.compute()
+
+
+def all_gather_shards(local, batch_sizes, group=None):
+    """Per-rank values of sharded global batches -> the global vector, in global order, on every rank.
+
+    local: this rank's values, its shard() slice of every batch in batch order (1-D).  Scores are not a sum, so the
+    one collective is an all_gather of fixed-size slices: every rank sends [count, values padded to the largest
+    rank's count] in fp64 (fp32 values travel exactly), and the counts that arrive are checked against shard()'s.
+    World size 1 needs no process group."""
+    d = _dist()
+    rank, world = (d.get_rank(group), d.get_world_size(group)) if d is not None else (0, 1)
+    local = local.reshape(-1).to(torch.float64)
+    sizes = [int(n) for n in batch_sizes]
+    per_rank = [sum(shard(n, r, world)[1] for n in sizes) for r in range(world)]
+    if local.numel() != per_rank[rank]:
+        raise ValueError("rank %d holds %d values, its shards hold %d" % (rank, local.numel(), per_rank[rank]))
+    if world == 1:
+        return local
+    buf = torch.zeros(1 + max(per_rank), dtype=torch.float64, device=local.device)
+    buf[0] = local.numel()
+    buf[1:1 + local.numel()] = local
+    got = [torch.empty_like(buf) for _ in range(world)]
+    d.all_gather(got, buf, group=group)
+    counts = [int(g[0].item()) for g in got]
+    if counts != per_rank:
+        raise RuntimeError("gathered shard counts %s, expected %s" % (counts, per_rank))
+    offs, parts = [1] * world, []
+    for n in sizes:  # global order: batch by batch, each batch's slices in rank order
+        for r in range(world):
+            c = shard(n, r, world)[1]
+            parts.append(got[r][offs[r]:offs[r] + c])
+            offs[r] += c
+    return torch.cat(parts) if parts else local
+
+
+def sharded_pr_auc(Q, G, E, batches, labels, g_l_steps=5, g_l_step_size=0.1, g_llhd_sigma=1.0, recon_weight=1.0,
+                   scorer=None):
+    """PR-AUC of the anomaly score over global batches, each split across ranks (eval_anomaly_det.py:100-126).
+
+    batches: iterable of global x batches (identical on every rank); labels: the global labels in the batches' order
+    (one vector, or one per batch), 1 = anomalous.  As in sharded_recon_mse, every rank draws the same global initial
+    latents and sweep key in q_forward's order and scores its slice with chain_base = the slice start
+    (anomaly.score), so the scores of the union of the shards are bitwise the 1-GPU run's; one all_gather at the end
+    (all_gather_shards), then every rank computes anomaly.pr_auc of the gathered vector.
+    scorer(xs, zt, seed, chain_base) -> (count,) scores replaces anomaly.score (tests of the gather)."""
+    from . import anomaly, langevin
+
+    if scorer is None:
+        def scorer(xs, zt, seed, chain_base):
+            return anomaly.score(Q, G, E, xs, g_l_steps=g_l_steps, g_l_step_size=g_l_step_size,
+                                 g_llhd_sigma=g_llhd_sigma, recon_weight=recon_weight, zt=zt, seed=seed,
+                                 chain_base=chain_base)[0]
+
+    d = _dist()
+    rank, world = (d.get_rank(), d.get_world_size()) if d is not None else (0, 1)
+    sizes, mine, device = [], [], None
+    for x in batches:
+        sizes.append(int(x.shape[0]))
+        s, c = shard(x.shape[0], rank, world)
+        # global draws, identical on every rank (host generator), in q_forward's order: zt, then the sweep key
+        zt = torch.randn(x.shape[0], Q.nz)
+        seed = langevin.new_seed() if Q.with_noise else 0
+        device = device or x.device
+        if c == 0:
+            continue
+        mine.append(scorer(x[s:s + c].contiguous(), zt[s:s + c], seed, s).reshape(-1))
+    local = torch.cat(mine) if mine else torch.zeros(0, dtype=torch.float32, device=device or "cpu")
+    scores = all_gather_shards(local, sizes).cpu().numpy()
+    parts = labels if isinstance(labels, (list, tuple)) else [labels]
+    y = torch.cat([torch.as_tensor(v).reshape(-1).cpu() for v in parts]).numpy()
+    return anomaly.pr_auc(y, scores)

@@ -184,6 +184,28 @@ int damc_z_update(float* z, const float* g, int batch, int nz, double step, int 
 int damc_philox_normal(float* out, int n_steps, int batch, int nz, uint64_t seed, uint64_t step_offset,
                        uint64_t chain_base, uint32_t stream_id, void* stream);
 
+/* ------------------------------------------------- per-sample posterior energy (anomaly score) */
+/* The anomaly drivers' score (workspace/eval_anomaly_det.py:114-117, train_anomaly_det.py:223-226) per sample, with
+ * a fixed summation order and no atomics: a row's result depends on that row's data and on the row length only --
+ * not on the batch size, the row's index or the other rows -- so shards of a batch reproduce the whole batch bit
+ * for bit.  Each row is cut into chunks of a fixed 16384 elements, one workgroup per (row, chunk); the chunk sums
+ * are added in chunk order.  A NULL or inconsistent argument and a workspace shorter than the query's answer both
+ * return DAMC_ERR_ARG on the host, before any launch. */
+/* per-op hook: out[b] = sum_j (xhat[b,j]-x[b,j])^2, fixed summation order, independent of batch composition */
+size_t damc_recon_rows_workspace_bytes(int batch, long row_elems);
+int damc_recon_rows(const float* xhat, const float* x, int batch, long row_elems, float* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* per-sample terms of U at a fixed z (z and x are read, never written):
+ *   terms (batch,3) = {|G(z)-x|^2, sum E(z) (0 if ebm == NULL), |z|^2/2};
+ *   score (batch) optional = recon_weight*terms[0] + terms[1] + terms[2], each operation rounded on its own;
+ *   xhat optional (G(z), forward layout).
+ * Runs damc_generator_forward's kernels (x_hat into the workspace when xhat == NULL), damc_ebm_energy_grad's
+ * per-chain energy, and the two kernels above. */
+size_t damc_posterior_energy_workspace_bytes(const damc_generator_t* g, int batch);
+int damc_posterior_energy(const damc_generator_t* g, const damc_ebm_t* ebm, const float* z, const float* x, int batch,
+                          float recon_weight, float* terms, float* score, float* xhat, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- Q amortizer (a8-a11) */
 /* generic fp32 MFMA implicit-GEMM conv (NHWC) + bias: encoder building block.  workspace (floats, may be
  * NULL / 0): split-K slabs for convolutions whose output tiles would not fill the chip, sized by
