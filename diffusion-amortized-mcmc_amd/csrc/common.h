@@ -60,12 +60,21 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 
 // uniform in (0, 1]: never 0, so log() is finite
 __device__ __forceinline__ float u01_open(uint32_t x) { return ((float)(x >> 8) + 1.0f) * (1.0f / 16777216.0f); }
+// uniform in [0, 1) on the 2^-24 grid: torch.rand's half-open interval (damc_philox_uniform, the seeded Q update's u)
+__device__ __forceinline__ float u01_halfopen(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
+
+// the Philox block of (chain, step, quad): counter = (quad, step lo, chain lo, stream_id ^ chain hi * golden),
+// key = (seed lo, seed hi ^ step hi)
+__device__ __forceinline__ Philox4 philox_block(uint64_t seed, uint64_t chain, uint64_t step, uint32_t quad,
+                                                uint32_t stream_id) {
+  return philox4x32_10(quad, (uint32_t)step, (uint32_t)chain, stream_id ^ (uint32_t)(chain >> 32) * 0x9E3779B9u,
+                       (uint32_t)seed, (uint32_t)(seed >> 32) ^ (uint32_t)(step >> 32));
+}
 
 // 4 N(0,1) values for (chain, step, quad) — element d of a chain uses quad d>>2, slot d&3
 __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t chain, uint64_t step, uint32_t quad,
                                                uint32_t stream_id, float out[4]) {
-  Philox4 r = philox4x32_10(quad, (uint32_t)step, (uint32_t)chain, stream_id ^ (uint32_t)(chain >> 32) * 0x9E3779B9u,
-                            (uint32_t)seed, (uint32_t)(seed >> 32) ^ (uint32_t)(step >> 32));
+  Philox4 r = philox_block(seed, chain, step, quad, stream_id);
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     float u1 = u01_open(r.v[2 * p]);
@@ -84,6 +93,10 @@ enum { DAMC_STREAM_POSTERIOR = 0x51, DAMC_STREAM_PRIOR = 0x52, DAMC_STREAM_SWEEP
 // the guided sweep's per-step prior-embedding noise, keyed (seed, chain_base + row, step k, quad): drawn by the caller
 // (damc_philox_normal), never by a kernel
 enum { DAMC_STREAM_GUIDE = 0x54 };
+// the seeded Q update (damc_q_noise_glue_seeded, Q.calculate_loss(seed=...)), keyed (seed, chain_base + row, step =
+// the update's draw_index): the schedule's u (word 0 of quad 0, [0, 1)), the forward diffusion's eps (drawn in-kernel)
+// and the prior-embedding noise (drawn by the caller, damc_philox_normal)
+enum { DAMC_STREAM_QU = 0x55, DAMC_STREAM_QEPS = 0x56, DAMC_STREAM_QPE = 0x57 };
 
 // element i & 3 of a 4-value draw without a runtime-indexed private array (which the compiler would place in
 // scratch memory: a per-dispatch scratch setup and slow private loads for every kernel that draws noise)

@@ -830,23 +830,19 @@ namespace {
 // input of Diffusion_UnetA.forward (:486-491) and its SinusoidalPosEmb (:447-461; the drop-in's fp64 sin / cos of the
 // fp32 angle, src/diffusion_net.py), each op rounded as PyTorch's ROCm kernels round it (no contraction; a division by
 // a Python scalar is a multiplication by its fp32 reciprocal): one thread per (sample, column) of max(nz, ntemb)
-__global__ void q_noise_glue_kernel(const float* __restrict__ u, const float* __restrict__ z,
-                                    const float* __restrict__ eps, int B, int nz, float lmin, float lmax,
-                                    const float* __restrict__ freqs, int ntemb, float* __restrict__ logsnr,
-                                    float* __restrict__ zt, float* __restrict__ temb) {
-  const int W = max(nz, ntemb);
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)B * W) return;
-  const int n = (int)(i / W), j = (int)(i - (long)n * W);
+__device__ __forceinline__ void q_noise_glue_elem(int n, int j, float un, const float* __restrict__ z, float epsv,
+                                                  int nz, float lmin, float lmax, const float* __restrict__ freqs,
+                                                  int ntemb, float* __restrict__ logsnr, float* __restrict__ zt,
+                                                  float* __restrict__ temb) {
   // logsnr_schedule_fn (diffusion_helper_func.py:41-50)
   const float b = atanf(expf(mul_rn(-0.5f, lmax)));
   const float a = sub_rn(atanf(expf(mul_rn(-0.5f, lmin))), b);
-  const float l = mul_rn(-2.0f, logf(tanf(add_rn(mul_rn(a, u[n]), b))));
+  const float l = mul_rn(-2.0f, logf(tanf(add_rn(mul_rn(a, un), b))));
   if (j == 0 && logsnr) logsnr[n] = l;
   if (j < nz) {  // diffusion_forward (:72-78): zt = z sqrt(sigmoid(l)) + sqrt(sigmoid(-l)) eps
     const float sp = 1.0f / add_rn(1.0f, expf(-l)), sm = 1.0f / add_rn(1.0f, expf(l));
     const long o = (long)n * nz + j;
-    zt[o] = add_rn(mul_rn(z[o], sqrtf(sp)), mul_rn(sqrtf(sm), eps[o]));
+    zt[o] = add_rn(mul_rn(z[o], sqrtf(sp)), mul_rn(sqrtf(sm), epsv));
   }
   const int half = ntemb / 2;
   if (j < half) {  // t_in = arctan(exp(-0.5 clamp(l, -20, 20))) / (pi / 2); x *= 1000 / max_time (max_time 1)
@@ -856,6 +852,44 @@ __global__ void q_noise_glue_kernel(const float* __restrict__ u, const float* __
     temb[(long)n * ntemb + j] = (float)sin((double)ang);
     temb[(long)n * ntemb + half + j] = (float)cos((double)ang);
   }
+}
+
+__global__ void q_noise_glue_kernel(const float* __restrict__ u, const float* __restrict__ z,
+                                    const float* __restrict__ eps, int B, int nz, float lmin, float lmax,
+                                    const float* __restrict__ freqs, int ntemb, float* __restrict__ logsnr,
+                                    float* __restrict__ zt, float* __restrict__ temb) {
+  const int W = max(nz, ntemb);
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * W) return;
+  const int n = (int)(i / W), j = (int)(i - (long)n * W);
+  q_noise_glue_elem(n, j, u[n], z, j < nz ? eps[(long)n * nz + j] : 0.f, nz, lmin, lmax, freqs, ntemb, logsnr, zt,
+                    temb);
+}
+
+// The same with u and eps drawn here (the seeded Q update): row n is chain chain_base + n at step draw_index; u is word
+// 0 of DAMC_STREAM_QU's quad-0 block on [0, 1) (damc_philox_uniform's value), eps element j the slot j & 3 of
+// DAMC_STREAM_QEPS's quad j >> 2 (damc_philox_normal's value).  Every thread of a row draws the row's u itself and its
+// own quad of eps (a row has <= max(nz, ntemb) threads: ten Philox rounds each, against the transcendental chain above)
+__global__ void q_noise_glue_seeded_kernel(const float* __restrict__ z, int B, int nz, float lmin, float lmax,
+                                           const float* __restrict__ freqs, int ntemb, uint64_t seed,
+                                           uint64_t draw_index, uint64_t chain_base, float* __restrict__ u_out,
+                                           float* __restrict__ eps, float* __restrict__ logsnr,
+                                           float* __restrict__ zt, float* __restrict__ temb) {
+  const int W = max(nz, ntemb);
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * W) return;
+  const int n = (int)(i / W), j = (int)(i - (long)n * W);
+  const uint64_t chain = chain_base + (uint64_t)n;
+  const float un = u01_halfopen(philox_block(seed, chain, draw_index, 0u, DAMC_STREAM_QU).v[0]);
+  if (j == 0 && u_out) u_out[n] = un;
+  float e = 0.f;
+  if (j < nz) {
+    float n4[4];
+    philox_normal4(seed, chain, draw_index, (uint32_t)(j >> 2), DAMC_STREAM_QEPS, n4);
+    e = pick4(n4, j);
+    eps[(long)n * nz + j] = e;
+  }
+  q_noise_glue_elem(n, j, un, z, e, nz, lmin, lmax, freqs, ntemb, logsnr, zt, temb);
 }
 
 // loss = 0.5 sum_j (eps - pred)^2 per sample (diffusion_net.py:642), and its gradient w.r.t. pred for an incoming
@@ -890,6 +924,19 @@ extern "C" int damc_q_noise_glue(const float* u, const float* z, const float* ep
   const long n = (long)batch * std::max(nz, ntemb);
   hipLaunchKernelGGL(damc::q_noise_glue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), u,
                      z, eps, batch, nz, logsnr_min, logsnr_max, freqs, ntemb, logsnr, zt, temb_in);
+  return (int)hipGetLastError();
+}
+
+extern "C" int damc_q_noise_glue_seeded(const float* z, int batch, int nz, float logsnr_min, float logsnr_max,
+                                        const float* freqs, int ntemb, uint64_t seed, uint64_t draw_index,
+                                        uint64_t chain_base, float* u, float* eps, float* logsnr, float* zt,
+                                        float* temb_in, void* stream) {
+  if (!z || !eps || !freqs || !zt || !temb_in || batch <= 0 || nz <= 0 || ntemb < 2 || ntemb % 2)
+    return DAMC_ERR_ARG;
+  const long n = (long)batch * std::max(nz, ntemb);
+  hipLaunchKernelGGL(damc::q_noise_glue_seeded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     as_stream(stream), z, batch, nz, logsnr_min, logsnr_max, freqs, ntemb, seed, draw_index,
+                     chain_base, u, eps, logsnr, zt, temb_in);
   return (int)hipGetLastError();
 }
 

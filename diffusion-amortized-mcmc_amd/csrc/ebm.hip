@@ -319,6 +319,15 @@ __global__ void philox_normal_kernel(float* out, int n_steps, int B, int nz, uin
   out[i] = pick4(n4, c);
 }
 
+// one U[0, 1) value per (step, row): word 0 of the block philox_normal4 draws for quad 0 of that (chain, step)
+__global__ void philox_uniform_kernel(float* out, int n_steps, int B, uint64_t seed, uint64_t step_offset,
+                                      uint64_t chain_base, uint32_t stream_id) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)n_steps * B) return;
+  const long st = i / B, r = i - st * B;
+  out[i] = u01_halfopen(philox_block(seed, chain_base + r, step_offset + st, 0u, stream_id).v[0]);
+}
+
 // ================================================================================================
 // Register-resident EBM (the default for nh <= 208, nz <= 128: _netE at every BASELINE config).
 //
@@ -960,6 +969,15 @@ extern "C" int damc_philox_normal(float* out, int n_steps, int B, int nz, uint64
   if (!out || n <= 0) return DAMC_ERR_ARG;
   hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), out,
                      n_steps, B, nz, seed, step_offset, chain_base, stream_id);
+  return (int)hipGetLastError();
+}
+
+extern "C" int damc_philox_uniform(float* out, int n_steps, int B, uint64_t seed, uint64_t step_offset,
+                                   uint64_t chain_base, uint32_t stream_id, void* stream) {
+  if (!out || n_steps <= 0 || B <= 0) return DAMC_ERR_ARG;
+  const long n = (long)n_steps * B;
+  hipLaunchKernelGGL(philox_uniform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), out,
+                     n_steps, B, seed, step_offset, chain_base, stream_id);
   return (int)hipGetLastError();
 }
 

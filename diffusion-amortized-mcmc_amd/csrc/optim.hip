@@ -183,6 +183,42 @@ __global__ __launch_bounds__(kThreads) void grad_scale_kernel(const AdamChunk* _
   for (int i = i0 + threadIdx.x; i < c.n; i += kThreads) G[i] = G[i] * coef;
 }
 
+// the gradient bucket of a data-parallel update: tensor t's elements, times scale, at bucket + off[t].  Source
+// pointers and offsets travel in the kernel arguments (1.5 KB); a NULL source (a parameter this rank has no gradient
+// for) contributes zeros.  The padding between slices is never written.
+struct PackArgs {
+  const float* g[DAMC_ADAM_MAX_TENSORS];
+  long long off[DAMC_ADAM_MAX_TENSORS];
+};
+static_assert(sizeof(PackArgs) + 64 <= 4096, "kernel argument block");
+
+__global__ __launch_bounds__(kThreads) void grad_pack_kernel(const AdamChunk* __restrict__ chunks, PackArgs t,
+                                                             float scale, float* __restrict__ bucket) {
+  const AdamChunk c = chunks[blockIdx.x];
+  float* D = bucket + t.off[c.tensor] + c.off;
+  const float* G = t.g[c.tensor];
+  if (!G) {
+    for (int i = threadIdx.x; i < c.n; i += kThreads) D[i] = 0.f;
+    return;
+  }
+  G += c.off;
+  int i0 = 0;
+  if (al16(G) && al16(D)) {
+    const int n4 = c.n >> 2;
+    for (int i = threadIdx.x; i < n4; i += kThreads) {
+      const f32x4 g = reinterpret_cast<const f32x4*>(G)[i];
+      f32x4 o;
+      o[0] = mul_rn(g[0], scale);
+      o[1] = mul_rn(g[1], scale);
+      o[2] = mul_rn(g[2], scale);
+      o[3] = mul_rn(g[3], scale);
+      reinterpret_cast<f32x4*>(D)[i] = o;
+    }
+    i0 = n4 << 2;
+  }
+  for (int i = i0 + threadIdx.x; i < c.n; i += kThreads) D[i] = mul_rn(G[i], scale);
+}
+
 bool fill(float* const* src, int n, float** dst) {
   if (!src || n < 0 || n > DAMC_ADAM_MAX_TENSORS) return false;
   for (int i = 0; i < n; ++i) {
@@ -265,6 +301,23 @@ int damc_grad_scale(const void* dev_chunks, int nchunks, float* const* grads, in
   if (nchunks == 0) return 0;
   grad_scale_kernel<<<nchunks, kThreads, 0, as_stream(stream)>>>(static_cast<const AdamChunk*>(dev_chunks), t,
                                                                   clip);
+  DAMC_LAUNCH_CHECK();
+  return 0;
+}
+
+int damc_grad_pack(const void* dev_chunks, int nchunks, const float* const* grads, const long long* bucket_off,
+                   int ntensors, float scale, float* bucket, void* stream) {
+  DAMC_REQUIRE(dev_chunks && grads && bucket_off && bucket && nchunks >= 0 && ntensors >= 0 &&
+               ntensors <= DAMC_ADAM_MAX_TENSORS);
+  PackArgs t;
+  for (int i = 0; i < DAMC_ADAM_MAX_TENSORS; ++i) {
+    t.g[i] = i < ntensors ? grads[i] : nullptr;  // NULL: zeros (fill() refuses it for the optimiser's calls)
+    t.off[i] = i < ntensors ? bucket_off[i] : 0;
+    DAMC_REQUIRE(t.off[i] >= 0);
+  }
+  if (nchunks == 0) return 0;
+  grad_pack_kernel<<<nchunks, kThreads, 0, as_stream(stream)>>>(static_cast<const AdamChunk*>(dev_chunks), t, scale,
+                                                                 bucket);
   DAMC_LAUNCH_CHECK();
   return 0;
 }

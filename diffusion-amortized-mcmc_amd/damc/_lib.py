@@ -21,6 +21,10 @@ LAYER_PROJ, LAYER_UP2, LAYER_SMALLC, LAYER_LINEAR = 1, 2, 3, 4
 ACT_NONE, ACT_LRELU, ACT_TANH = 0, 1, 2
 ACT_RELU = 4  # damc_mlp_forward
 
+# csrc/common.h Philox stream ids
+STREAM_POSTERIOR, STREAM_PRIOR, STREAM_SWEEP, STREAM_GUIDE = 0x51, 0x52, 0x53, 0x54
+STREAM_QU, STREAM_QEPS, STREAM_QPE = 0x55, 0x56, 0x57  # the seeded Q update: u, eps, prior-embedding noise
+
 c_float_p = ctypes.POINTER(ctypes.c_float)
 
 
@@ -193,6 +197,7 @@ _SIGS = {
     "damc_prior_emb_train_backward": (_I, [ctypes.POINTER(PriorEmb), _P, _P, _P, _I, ctypes.POINTER(PriorEmbGrads), _P,
                                            _SZ, _P]),
     "damc_q_noise_glue": (_I, [_P, _P, _P, _I, _I, _F, _F, _P, _I, _P, _P, _P, _P]),
+    "damc_q_noise_glue_seeded": (_I, [_P, _I, _I, _F, _F, _P, _I, _U64, _U64, _U64, _P, _P, _P, _P, _P, _P]),
     "damc_q_loss_forward": (_I, [_P, _P, _I, _I, _P, _P]),
     "damc_q_loss_backward": (_I, [_P, _P, _P, ctypes.c_long, _I, _I, _P, _P]),
     "damc_prior_langevin": (_I, [ctypes.POINTER(Ebm), _P, _I, _I, _D, _I, _P, _U64, _U64, _U64, _P, _P]),
@@ -201,6 +206,7 @@ _SIGS = {
     "damc_ebm_energy_grad": (_I, [ctypes.POINTER(Ebm), _P, _I, _P, _P, _P]),
     "damc_z_update": (_I, [_P, _P, _I, _I, _D, _I, _P, _U64, _U64, _U64, _P]),
     "damc_philox_normal": (_I, [_P, _I, _I, _I, _U64, _U64, _U64, ctypes.c_uint32, _P]),
+    "damc_philox_uniform": (_I, [_P, _I, _I, _U64, _U64, _U64, ctypes.c_uint32, _P]),
     "damc_recon_rows_workspace_bytes": (_SZ, [_I, ctypes.c_long]),
     "damc_recon_rows": (_I, [_P, _P, _I, ctypes.c_long, _P, _P, _SZ, _P]),
     "damc_posterior_energy_workspace_bytes": (_SZ, [ctypes.POINTER(Generator), _I]),
@@ -256,6 +262,7 @@ _SIGS = {
     "damc_grad_sumsq": (_I, [_P, _I, _P, _I, _P, _P]),
     "damc_grad_norm_finish": (_I, [_P, _I, _F, _P, _P]),
     "damc_grad_scale": (_I, [_P, _I, _P, _I, _P, _P]),
+    "damc_grad_pack": (_I, [_P, _I, _P, ctypes.POINTER(ctypes.c_longlong), _I, _F, _P, _P]),
     "damc_adam_step": (_I, [_P, _I, _P, _P, _P, _P, _I, ctypes.POINTER(AdamHparams), _P, _P]),
     "damc_specnorm_workspace_bytes": (_SZ, [ctypes.POINTER(SpecNormLayer), _I]),
     "damc_specnorm_forward": (_I, [ctypes.POINTER(SpecNormLayer), _I, _I, _P, _SZ, _P]),

@@ -9,7 +9,14 @@ RCCL/xGMI for backend "nccl", or gloo in the CPU tests):
   * reconstruction MSE (eval_gen_recon.py:177-212): [sum of per-sample MSE, count];
   * FID sufficient statistics (MCMC.py:130-176 feed pfw.fid): [sum f, sum f f^T, n] in fp64;
 and, for the anomaly score, which is not a sum, one ``all_gather`` of fixed-size slices (``all_gather_shards``).
+
+Data-parallel updates: each rank runs the G / Q / E update's forward and backward on its shard of the
+batch (the seeded ``Q.calculate_loss`` keys its draws by the global row), ``GradBucket`` packs the net's gradients into
+one flat buffer scaled by local / global batch, one ``all_reduce(SUM)`` sums the ranks' buffers, the gradients become
+views of the buffer and the usual clip + Adam kernels run on those views (``sharded_step``).
 """
+import ctypes
+
 import torch
 
 
@@ -202,3 +209,181 @@ def sharded_pr_auc(Q, G, E, batches, labels, g_l_steps=5, g_l_step_size=0.1, g_l
     parts = labels if isinstance(labels, (list, tuple)) else [labels]
     y = torch.cat([torch.as_tensor(v).reshape(-1).cpu() for v in parts]).numpy()
     return anomaly.pr_auc(y, scores)
+
+
+# ------------------------------------------------------------------------------------- data-parallel updates
+def bucket_layout(numels):
+    """(offsets, total) of a gradient bucket: prefix sums of the sizes rounded up to 4 elements, so every slice of a
+    16-byte aligned buffer is 16-byte aligned and the clip norm over the slices takes grad_sumsq_kernel's vector path,
+    in the same order as over separately allocated gradients."""
+    offs, off = [], 0
+    for n in numels:
+        offs.append(off)
+        off += (int(n) + 3) // 4 * 4
+    return offs, off
+
+
+def iteration_seed(base_seed, iteration, purpose=0):
+    """A 62-bit Philox seed for (base_seed, iteration, purpose): a pure host hash (splitmix64's finaliser over the
+    three words), equal on every rank without a collective.  purpose separates the seeds one iteration needs (the Q
+    sweep, the posterior chains, the prior chains, the Q update, ...)."""
+    m = (1 << 64) - 1
+    h = 0
+    for w in (int(base_seed), int(iteration), int(purpose)):
+        h = (h + (w & m) + 0x9E3779B97F4A7C15) & m
+        h = ((h ^ (h >> 30)) * 0xBF58476D1CE4E5B9) & m
+        h = ((h ^ (h >> 27)) * 0x94D049BB133111EB) & m
+        h ^= h >> 31
+    return h >> 2
+
+
+def grad_pack(grads, numels, offsets, bucket, scale):
+    """bucket[offsets[t] : offsets[t] + numels[t]] = grads[t] * scale (damc_grad_pack), one launch per 96 tensors; a
+    None gradient writes zeros.  The elements between the slices are left as they are."""
+    from . import _lib, optim
+
+    f32, strided = torch.float32, torch.strided
+    for t in (*grads, bucket):
+        # optim._require_fp32_cuda, as one expression on the common case (optim.Adam._collect does the same)
+        if t is not None and not (t.dtype is f32 and t.is_cuda and t.layout is strided and t.is_contiguous()):
+            optim._require_fp32_cuda(t, "grad_pack")
+    if len(grads) != len(numels) or len(grads) != len(offsets) or any(
+            g is not None and g.numel() != n for g, n in zip(grads, numels)):
+        raise _lib.DamcError("grad_pack: gradients, sizes and offsets disagree")
+    if any(o < 0 or o + n > bucket.numel() for o, n in zip(offsets, numels)):
+        raise _lib.DamcError("grad_pack: a slice lies outside the bucket")
+    chunks = optim._Chunks.of(list(numels), bucket.device)
+    L, s = _lib.lib(), optim._stream()
+    for t0, t1, dev, n, _ in chunks.slices:
+        ptrs = (ctypes.c_void_p * (t1 - t0))(*[g.data_ptr() if g is not None else None for g in grads[t0:t1]])
+        offs = (ctypes.c_longlong * (t1 - t0))(*offsets[t0:t1])
+        optim._check(L.damc_grad_pack(ctypes.c_void_p(dev.data_ptr()), n, ptrs, offs, t1 - t0, float(scale),
+                                      ctypes.c_void_p(bucket.data_ptr()), s), "damc_grad_pack")
+    return bucket
+
+
+class _Layout:
+    def __init__(self, index, numels, device):
+        self.index, self.numels = index, numels
+        self.offsets, self.total = bucket_layout(numels)
+        self.buffer = torch.empty(max(self.total, 4), dtype=torch.float32, device=device)
+        self.buffer.zero_()  # the padding between slices stays zero: pack never writes it
+        self.host = None     # pinned staging buffer of the gloo route
+        self.views = None    # the slices as the parameters' shapes, made on the first attach
+
+
+class GradBucket:
+    """One flat fp32 buffer for the gradients of ``params``, for a single all_reduce per update.
+
+    The layout covers the parameters whose ``.grad`` is not None, in order (``optim.Adam._collect``'s rule); the slice
+    offsets are ``bucket_layout``'s.  The layout and its buffer are cached per (device, index / size tuple), so an
+    update whose set of gradients repeats allocates nothing.  ``pack`` -> ``all_reduce`` -> ``attach`` leaves every
+    covered ``p.grad`` a view of the reduced buffer: there is no unpack pass, the clip norm and the Adam step read the
+    slices through their pointer tables as they read any gradient."""
+
+    def __init__(self, params):
+        self.params = [p for p in params]
+        self._layouts = {}
+        self.layout = None
+
+    def _current(self):
+        from . import _lib
+
+        index = tuple(i for i, p in enumerate(self.params) if p.grad is not None)
+        if not index:
+            raise _lib.DamcError("GradBucket: no parameter has a gradient")
+        grads = [self.params[i].grad for i in index]
+        dev = grads[0].device
+        if dev.type != "cuda":
+            raise _lib.DamcError("GradBucket: the gradients must be on a ROCm device (got %s); the pack kernel has no "
+                                 "CPU fallback" % dev)
+        numels = tuple(g.numel() for g in grads)
+        key = (str(dev), index, numels)
+        lay = self._layouts.get(key)
+        if lay is None:
+            if len(self._layouts) > 16:
+                self._layouts.clear()
+            lay = self._layouts[key] = _Layout(index, numels, dev)
+        self.layout = lay
+        return lay, grads
+
+    @property
+    def buffer(self):
+        return self.layout.buffer if self.layout is not None else None
+
+    @torch.no_grad()
+    def pack(self, scale=1.0):
+        """buffer slice t = grad t * scale, for the parameters that have a gradient now; returns the buffer."""
+        lay, grads = self._current()
+        return grad_pack(grads, lay.numels, lay.offsets, lay.buffer, scale)
+
+    def all_reduce(self, group=None):
+        """One SUM all_reduce of the flat buffer.  RCCL reduces in place; under a gloo group a device buffer is staged
+        through a pinned host tensor (ranks that share one GPU in the tests; bench.py reduces on the CPU under gloo)."""
+        d = _dist()
+        lay = self.layout
+        if lay is None:
+            raise RuntimeError("GradBucket.all_reduce before pack")
+        if d is None or d.get_world_size(group) == 1:
+            return lay.buffer
+        if d.get_backend(group) == "gloo" and lay.buffer.is_cuda:
+            if lay.host is None:
+                lay.host = torch.empty(lay.buffer.shape, dtype=torch.float32).pin_memory()
+            lay.host.copy_(lay.buffer)  # a blocking device-to-host copy: ordered after pack on the current stream
+            d.all_reduce(lay.host, op=d.ReduceOp.SUM, group=group)
+            lay.buffer.copy_(lay.host, non_blocking=True)
+        else:
+            d.all_reduce(lay.buffer, op=d.ReduceOp.SUM, group=group)
+        return lay.buffer
+
+    def attach(self):
+        """p.grad = the buffer's slice, viewed as p, for every covered parameter."""
+        lay = self.layout
+        if lay is None:
+            raise RuntimeError("GradBucket.attach before pack")
+        if lay.views is None:  # the same view objects every update: ~100 slices + reshapes are host time otherwise
+            lay.views = [lay.buffer[off:off + n].view_as(self.params[i])
+                         for i, off, n in zip(lay.index, lay.offsets, lay.numels)]
+        for i, v in zip(lay.index, lay.views):
+            self.params[i].grad = v
+
+    def verify(self, group=None):
+        """Debug check, not on the step's path: every rank must hold gradients for the same parameters (one
+        all_gather_object of the (index, numel) tuples); raises RuntimeError on every rank if they disagree."""
+        index = tuple(i for i, p in enumerate(self.params) if p.grad is not None)
+        mine = (index, tuple(self.params[i].grad.numel() for i in index))
+        d = _dist()
+        if d is None or d.get_world_size(group) == 1:
+            return
+        got = [None] * d.get_world_size(group)
+        d.all_gather_object(got, mine, group=group)
+        if any(g != got[0] for g in got):
+            bad = [r for r, g in enumerate(got) if g != got[0]]
+            raise RuntimeError("GradBucket.verify: ranks %s hold gradients for other parameters than rank 0 (%s)"
+                               % (bad, [len(g[0]) for g in got]))
+
+
+def sharded_step(optimizer, local_batch, global_batch, max_norm=None, group=None, verify=False):
+    """The data-parallel form of clip + step, after this rank's backward over its ``local_batch`` rows of the
+    ``global_batch``: pack the gradients scaled by local / global (every loss of the drivers is a mean over the local
+    rows, so the sum over ranks is the global mean's gradient), one all_reduce, gradients re-pointed at the reduced
+    buffer, then ``optimizer.clip_and_step(max_norm)`` (damc.optim) -- ``step()`` when max_norm is None; a stock
+    optimiser gets clip_grad_norm_ followed by step().  Returns the total norm, or None.  A world of 1 takes the same
+    path (pack and attach, no collective)."""
+    bucket = getattr(optimizer, "_damc_grad_bucket", None)
+    params = [p for g in optimizer.param_groups for p in g["params"]]
+    if bucket is None or len(bucket.params) != len(params) or any(a is not b for a, b in zip(bucket.params, params)):
+        bucket = optimizer._damc_grad_bucket = GradBucket(params)
+    if verify:
+        bucket.verify(group)
+    bucket.pack(float(local_batch) / float(global_batch))
+    bucket.all_reduce(group)
+    bucket.attach()
+    if max_norm is None:
+        optimizer.step()
+        return None
+    if hasattr(optimizer, "clip_and_step"):
+        return optimizer.clip_and_step(max_norm)
+    norm = torch.nn.utils.clip_grad_norm_(params, max_norm)
+    optimizer.step()
+    return norm

@@ -191,6 +191,15 @@ def philox_normal(n_steps, batch, nz, seed, device, step_offset=0, chain_base=0,
     return out
 
 
+def philox_uniform(n_steps, batch, seed, device, step_offset=0, chain_base=0, stream_id=_lib.STREAM_QU):
+    """(n_steps, batch) U[0, 1) values on the 2^-24 grid (torch.rand's interval), keyed like philox_normal: row r of
+    step i is word 0 of the block of (seed, chain_base + r, step_offset + i, quad 0, stream_id)."""
+    out = torch.empty(n_steps, batch, dtype=torch.float32, device=device)
+    check(_lib.lib().damc_philox_uniform(ptr(out), n_steps, batch, seed, step_offset, chain_base, stream_id,
+                                         _lib.stream_ptr(device)), "damc_philox_uniform")
+    return out
+
+
 def z_update(z, g, step, with_noise, noise=None, seed=0, step_index=0, chain_base=0):
     """Per-op hook: z <- z - 0.5 step^2 (g + z) (+ step xi), in place (MCMC.py:36-38,62-64)."""
     _f32c(z, "z")

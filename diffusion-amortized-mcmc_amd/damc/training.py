@@ -455,6 +455,28 @@ def q_noise_glue(q, u, z, eps, logsnr_out=None):
     return zt, se
 
 
+def q_noise_glue_seeded(q, z, seed, draw_index=0, chain_base=0, u_out=None, logsnr_out=None):
+    """(zt, temb_in, eps) of the seeded Q.calculate_loss in one launch (damc_q_noise_glue_seeded): q_noise_glue with u
+    and eps drawn in the kernel from the Philox streams STREAM_QU / STREAM_QEPS, keyed (seed, chain_base + row,
+    draw_index) -- a row's noise depends on its global index and the update's index, not on the rank that holds it.
+    u_out (B) / logsnr_out (B) receive the draws' u and the schedule's logsnr (tests)."""
+    if z.device.type != "cuda" or z.dtype != torch.float32 or z.dim() != 2:
+        raise _lib.DamcError("q_noise_glue_seeded: z must be a (B, nz) float32 tensor on a ROCm device (got %s %s); the "
+                             "seeded draws have no CPU fallback" % (z.dtype, z.device))
+    B, nz = z.shape
+    ntemb = q.p.ntemb
+    dev = z.device
+    z = z.contiguous()
+    zt = torch.empty(B, nz, dtype=torch.float32, device=dev)
+    se = torch.empty(B, ntemb, dtype=torch.float32, device=dev)
+    eps = torch.empty(B, nz, dtype=torch.float32, device=dev)
+    check(_lib.lib().damc_q_noise_glue_seeded(ptr(z), B, nz, float(q.logsnr_min), float(q.logsnr_max),
+                                              ptr(_freqs(ntemb // 2, dev)), ntemb, int(seed), int(draw_index),
+                                              int(chain_base), ptr(u_out), ptr(eps), ptr(logsnr_out), ptr(zt), ptr(se),
+                                              _lib.stream_ptr(dev)), "damc_q_noise_glue_seeded")
+    return zt, se, eps
+
+
 class _QLossFn(torch.autograd.Function):
     """0.5 * sum((eps - eps_pred) ** 2, dim=1) (diffusion_net.py:642) as one kernel each way."""
 

@@ -317,7 +317,7 @@ class _QBase(nn.Module):
         """xemb of calculate_loss: the encoder under autograd (_EncoderBase.forward picks libdamc's training path)."""
         return self.encoder(x)
 
-    def calculate_loss(self, x=None, z=None, mask=None):
+    def calculate_loss(self, x=None, z=None, mask=None, seed=None, draw_index=0, chain_base=0):
         """Training loss of the denoiser (diffusion_net.py:624-645; the toy's is the same lines,
         toy_example/src/diffusion_net.py:241-263).  On ROCm tensors the denoiser's forward and
         backward run on libdamc (Diffusion_UnetA.forward -> damc.training.denoiser_apply), as do the encoder's
@@ -326,8 +326,16 @@ class _QBase(nn.Module):
         damc.training.prior_emb_apply); the random draws stay torch's, in the reference's order.  The toy's denoiser
         (nz = 2) takes the same route, and its MLP encoder and prior_emb the fused MLP's training calls
         (damc.training.mlp_apply, _netQ_U_toy._encode_for_loss).  A denoiser the training kernels do not take
-        (damc.training.denoiser_train_supported) runs on its stock layers under autograd."""
+        (damc.training.denoiser_train_supported) runs on its stock layers under autograd.
+
+        seed (data-parallel training): the three draws come from libdamc's Philox streams keyed (seed, chain_base + row,
+        draw_index) instead of torch's generator -- prior_emb's noise from damc.langevin.philox_normal (STREAM_QPE), u
+        and eps inside the noising launch (damc.training.q_noise_glue_seeded) -- so a row's noise depends on its global
+        index and the update's index only, whichever rank holds it; no torch generator is consulted.  The seeded draws
+        exist on the libdamc path alone: anything else raises DamcError."""
         assert z is not None
+        if seed is not None:
+            return self._calculate_loss_seeded(x, z, mask, seed, draw_index, chain_base)
         if x is not None:
             xemb = self._encode_for_loss(x)
             if mask is not None:
@@ -355,6 +363,31 @@ class _QBase(nn.Module):
         eps_pred = self.p(z=fwd["mean"] + fwd["std"] * eps, logsnr=logsnr, xemb=xemb)
         assert eps.shape == eps_pred.shape == (len(z), self.nz)
         return 0.5 * torch.sum((eps - eps_pred) ** 2, dim=1)
+
+
+    def _calculate_loss_seeded(self, x, z, mask, seed, draw_index, chain_base):
+        from damc import _lib, langevin, training
+
+        if not (z.is_cuda and z.dtype == torch.float32 and not z.requires_grad and (x is None or x.is_cuda)):
+            raise _lib.DamcError("calculate_loss(seed=...): z (and x) must be float32 ROCm tensors without grad; the "
+                                 "seeded draws have no CPU fallback")
+        if not (training.ENABLED and training.Q_GLUE and training.denoiser_train_supported(self.p)):
+            raise _lib.DamcError("calculate_loss(seed=...): the libdamc Q update is off (stock_pytorch / DAMC_Q_GLUE=0) "
+                                 "or does not take this denoiser; the seeded draws exist on that path only")
+        assert x is not None or mask is None
+
+        def prior_noise(n):
+            return langevin.philox_normal(1, n, self.nz, seed, z.device, step_offset=draw_index, chain_base=chain_base,
+                                          stream_id=_lib.STREAM_QPE)[0]
+
+        if x is not None:
+            xemb = self._encode_for_loss(x)
+            if mask is not None:
+                xemb = xemb * mask + self._prior_emb(prior_noise(len(x))) * (1 - mask)
+        else:
+            xemb = self._prior_emb(prior_noise(len(z)))
+        zt, se, eps = training.q_noise_glue_seeded(self, z, seed, draw_index, chain_base)
+        return training.q_loss(eps, training.denoiser_apply(self.p, zt, se, xemb))
 
 
 class _netQ_U(_QBase):

@@ -22,7 +22,10 @@
  *     Philox4x32-10 keyed by (seed) with counter (dim/4, step + step_offset,
  *     chain_base + chain, stream_id): a chain's noise depends on its GLOBAL index only, so
  *     results are identical for any sharding of the batch over GPUs.  noise != NULL
- *     injects (n_steps, B, nz) values instead (parity tests).
+ *     injects (n_steps, B, nz) values instead (parity tests).  Stream ids: 0x51 posterior chains, 0x52 prior
+ *     chains, 0x53 the reverse sweep, 0x54 the guided sweep's prior-embedding noise, and for the seeded Q update
+ *     (step = the update's draw_index) 0x55 DAMC_STREAM_QU the schedule's u, 0x56 DAMC_STREAM_QEPS the forward
+ *     diffusion's eps, 0x57 DAMC_STREAM_QPE the prior-embedding noise of Q.calculate_loss.
  */
 #ifndef DAMC_H
 #define DAMC_H
@@ -183,6 +186,11 @@ int damc_z_update(float* z, const float* g, int batch, int nz, double step, int 
 /* Philox N(0,1) draw used by every Langevin kernel (statistical tests) -> out (n_steps,B,nz) */
 int damc_philox_normal(float* out, int n_steps, int batch, int nz, uint64_t seed, uint64_t step_offset,
                        uint64_t chain_base, uint32_t stream_id, void* stream);
+/* One U[0, 1) value per (step, row) -> out (n_steps, B): word 0 of the Philox block damc_philox_normal draws for
+ * (seed, chain_base + row, step_offset + step, quad 0, stream_id), as (float)(word >> 8) * 2^-24 -- torch.rand's
+ * half-open interval on the 2^-24 grid (the normals keep their (0, 1] uniforms). */
+int damc_philox_uniform(float* out, int n_steps, int batch, uint64_t seed, uint64_t step_offset, uint64_t chain_base,
+                        uint32_t stream_id, void* stream);
 
 /* ------------------------------------------------- per-sample posterior energy (anomaly score) */
 /* The anomaly drivers' score (workspace/eval_anomaly_det.py:114-117, train_anomaly_det.py:223-226) per sample, with
@@ -517,6 +525,15 @@ int damc_denoiser_train_backward(const damc_denoiser_train_t* d, const float* gr
 int damc_q_noise_glue(const float* u, const float* z, const float* eps, int batch, int nz, float logsnr_min,
                       float logsnr_max, const float* freqs, int ntemb, float* logsnr, float* zt, float* temb_in,
                       void* stream);
+/* damc_q_noise_glue with its draws made in the same launch (the data-parallel Q update): u (B) from stream 0x55 as
+ * damc_philox_uniform gives it, eps (B, nz) from stream 0x56 as damc_philox_normal gives it, both keyed (seed,
+ * chain_base + row, step draw_index), so a row's noise depends on its GLOBAL index and the update's index only.  eps is
+ * written (the loss reads it); u and logsnr are written when non-NULL.  zt, temb_in and logsnr are bitwise what
+ * damc_q_noise_glue gives when fed the u and eps this call returns.  Any nz damc_q_noise_glue takes; bad arguments
+ * return DAMC_ERR_ARG. */
+int damc_q_noise_glue_seeded(const float* z, int batch, int nz, float logsnr_min, float logsnr_max, const float* freqs,
+                             int ntemb, uint64_t seed, uint64_t draw_index, uint64_t chain_base, float* u, float* eps,
+                             float* logsnr, float* zt, float* temb_in, void* stream);
 /* loss (B) = 0.5 * sum_j (eps - eps_pred)^2 (diffusion_net.py:642), and grad_eps_pred (B, nz) from grad_loss (B, element
  * stride grad_stride: 0 for the broadcast gradient of a .mean()) */
 int damc_q_loss_forward(const float* eps, const float* eps_pred, int batch, int nz, float* loss, void* stream);
@@ -625,6 +642,14 @@ int damc_grad_norm_finish(const float* partial, int n, float max_norm, float* ou
 /* grads *= clip[1] (the second half of clip_grad_norm_) */
 int damc_grad_scale(const void* dev_chunks, int nchunks, float* const* grads, int ntensors, const float* clip,
                     void* stream);
+/* gradient bucket of a data-parallel update: bucket[bucket_off[t] + i] = grads[t][i] * scale over the chunk table of
+ * the tensors' sizes (one fp32 multiply, rounded on its own); grads[t] == NULL writes zeros.  grads and bucket_off
+ * (element offsets, >= 0) are host arrays of ntensors (<= DAMC_ADAM_MAX_TENSORS) entries that travel in the kernel
+ * arguments.  16-byte accesses where the source and the destination slice are both 16-byte aligned, scalar ones
+ * otherwise (the same values).  Elements between the slices are not written.  The other calls of this section take
+ * arbitrary pointers, so after the reduce they run on the bucket's slices: there is no unpack. */
+int damc_grad_pack(const void* dev_chunks, int nchunks, const float* const* grads, const long long* bucket_off,
+                   int ntensors, float scale, float* bucket, void* stream);
 /* one Adam/AdamW step over every chunk (params, grads, exp_avgs, exp_avg_sqs: host arrays of device
  * pointers); clip (device, from damc_grad_norm) or NULL: when given, the gradient is scaled by clip[1]
  * first and written back, as clip_grad_norm_ would have left it */
