@@ -607,6 +607,8 @@ int setup(const damc_denoiser_train_t* d, int B, void* wsp, size_t wsb, DW* w) {
   if (B <= 0) return DAMC_ERR_ARG;
   const size_t need = carve(d, B, nullptr, nullptr);
   if (!wsp || wsb < need) return DAMC_ERR_WORKSPACE;
+  // the carve's regions are the float4 operands of every product: the one alignment these calls require (damc.h)
+  if (reinterpret_cast<uintptr_t>(wsp) & 15) return DAMC_ERR_UNSUPPORTED;
   carve(d, B, reinterpret_cast<char*>(wsp), w);
   return 0;
 }
@@ -624,8 +626,20 @@ int forward(const damc_denoiser_train_t* d, const float* zt, const float* se, co
     ProfScope ps("dn_pack", 0.0, s);
     Packer pk(s);
     const int pad6 = w.lay[6] - d->blocks[6].dout;  // out2's zero columns (nz % 4 != 0 only)
-    if (w.narrow)  // out2's packed weights and biases (one contiguous run of the carve): zero, then the real corners
-      DAMC_CHECK(hipMemsetAsync(w.WLS_T[6], 0, (size_t)((char*)w.WC_T - (char*)w.WLS_T[6]), s));
+    if (w.narrow) {
+      // out2's packed weights and biases: zero, then the real corners.  The zeros are a launch of the pack kernel, not a
+      // memset: in a replay of a captured graph a memset node was not ordered before the kernels that follow it in the
+      // stream, and the backward multiplies the pad rows by the zero pad gradients: leftover NaN bits
+      // there would reach every gradient of a captured Q update
+      const int di6 = d->blocks[6].din, l6 = w.lay[6];
+      pk.add(nullptr, di6, 2 * l6, nullptr, 0, 0, w.WLS_T[6], 2 * l6, 0);
+      pk.add(nullptr, 2 * l6, di6, nullptr, 0, 0, w.WLS[6], di6, 0);
+      pk.add(nullptr, l6, 2 * l6, nullptr, 0, 0, w.WBG_T[6], 2 * l6, 0);
+      pk.add(nullptr, 2 * l6, l6, nullptr, 0, 0, w.WBG[6], l6, 0);
+      pk.add(nullptr, 2 * l6, 1, nullptr, 0, 0, w.bLS[6], 1, 0);
+      pk.add(nullptr, 2 * l6, 1, nullptr, 0, 0, w.bBG[6], 1, 0);
+      pk.flush();
+    }
     for (int b = 0; b < 7; ++b) {
       const damc_csq_block_t& k = d->blocks[b];
       const int di = k.din, dd = k.dout, ld = w.lay[b];  // ld = dd but for the padded out2

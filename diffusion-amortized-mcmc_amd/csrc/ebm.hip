@@ -1030,9 +1030,13 @@ size_t et_carve(int nh, int B, char* base, EtWs* w) {
   if (w) *w = t;
   return off;
 }
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the backward's LReLU' comes from the post-activation's sign (et_dh2_kernel / et_mask_kernel): the pre-activation's
+// only for slope >= 0.  The forward reads w1..w3 as float4 rows (the grouped kernel's b_t operand): 16-B aligned, checked
+// here so that a call is refused before its first launch and the workspace query returns 0 for such a descriptor
 bool et_ok(const damc_ebm_t* e, int B) {
-  return e && e->nz > 0 && e->nh > 0 && B > 0 && B % 4 == 0 && e->nz % 4 == 0 && e->nh % 4 == 0 && e->w1 && e->b1 &&
-         e->w2 && e->b2 && e->w3 && e->b3;
+  return e && e->nz > 0 && e->nh > 0 && B > 0 && B % 4 == 0 && e->nz % 4 == 0 && e->nh % 4 == 0 && e->slope >= 0.f &&
+         e->w1 && e->b1 && e->w2 && e->b2 && e->w3 && e->b3 && al16(e->w1) && al16(e->w2) && al16(e->w3);
 }
 // dh2 = (g w3) * lrelu'(h2), its transpose, and g as a contiguous row
 __global__ void et_dh2_kernel(const float* __restrict__ g, long gs, const float* __restrict__ w3,
@@ -1098,6 +1102,7 @@ extern "C" int damc_ebm_train_forward(const damc_ebm_t* e, const float* z, int B
                                       void* stream) {
   if (!e || !z || !h1 || !h2 || !energy) return DAMC_ERR_ARG;
   if (!et_ok(e, B)) return DAMC_ERR_UNSUPPORTED;
+  if (!al16(z) || !al16(h1) || !al16(h2)) return DAMC_ERR_UNSUPPORTED;  // the three products' float4 A rows
   hipStream_t s = as_stream(stream);
   const int nz = e->nz, nh = e->nh;
   const damc::SmallGemm l1 = sg(z, nz, e->w1, nz, 1, e->b1, h1, nh, B, nh, nz, DAMC_ACT_LRELU, e->slope);
@@ -1116,6 +1121,7 @@ extern "C" int damc_ebm_train_backward(const damc_ebm_t* e, const float* z, cons
   if (!et_ok(e, B)) return DAMC_ERR_UNSUPPORTED;
   const int nz = e->nz, nh = e->nh;
   if (!workspace || workspace_bytes < et_carve(nh, B, nullptr, nullptr)) return DAMC_ERR_WORKSPACE;
+  if (!al16(workspace)) return DAMC_ERR_UNSUPPORTED;  // every float4 A operand of the backward is a region of it
   EtWs w;
   et_carve(nh, B, static_cast<char*>(workspace), &w);
   hipStream_t s = as_stream(stream);
@@ -1170,7 +1176,7 @@ size_t pe_carve(const damc_prior_emb_t* e, int B, char* base, PeWs* w) {
 // the backward's LReLU' comes from the post-activation's sign: the pre-activation's only for slope >= 0
 bool pe_ok(const damc_prior_emb_t* e, int B) {
   return e && e->nz > 0 && e->nh > 0 && e->nout > 0 && B > 0 && B % 4 == 0 && e->nz % 4 == 0 && e->nh % 4 == 0 &&
-         e->nout % 4 == 0 && e->slope >= 0.f && e->w1 && e->b1 && e->w2 && e->b2;
+         e->nout % 4 == 0 && e->slope >= 0.f && e->w1 && e->b1 && e->w2 && e->b2 && al16(e->w1) && al16(e->w2);
 }
 }  // namespace
 
@@ -1183,6 +1189,7 @@ extern "C" int damc_prior_emb_train_forward(const damc_prior_emb_t* e, const flo
                                             void* stream) {
   if (!e || !noise || !h || !out) return DAMC_ERR_ARG;
   if (!pe_ok(e, B)) return DAMC_ERR_UNSUPPORTED;
+  if (!al16(noise) || !al16(h)) return DAMC_ERR_UNSUPPORTED;  // the two products' float4 A rows
   hipStream_t s = as_stream(stream);
   const damc::SmallGemm l1 = sg(noise, e->nz, e->w1, e->nz, 1, e->b1, h, e->nh, B, e->nh, e->nz, DAMC_ACT_LRELU, e->slope);
   const damc::SmallGemm l2 = sg(h, e->nh, e->w2, e->nh, 1, e->b2, out, e->nout, B, e->nout, e->nh, DAMC_ACT_NONE, 0.f);
@@ -1197,6 +1204,8 @@ extern "C" int damc_prior_emb_train_backward(const damc_prior_emb_t* e, const fl
   if (!e || !noise || !h || !grad_out || !gr) return DAMC_ERR_ARG;
   if (!pe_ok(e, B)) return DAMC_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < pe_carve(e, B, nullptr, nullptr)) return DAMC_ERR_WORKSPACE;
+  // the float4 A operands of the backward: grad_out itself (the hidden gradient's product) and regions of the workspace
+  if (!al16(workspace) || !al16(grad_out)) return DAMC_ERR_UNSUPPORTED;
   PeWs w;
   pe_carve(e, B, static_cast<char*>(workspace), &w);
   hipStream_t s = as_stream(stream);

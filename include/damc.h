@@ -499,7 +499,17 @@ int damc_guided_sweep(const damc_denoiser_t* d, const float* xemb, const float* 
  * 490-491).  nz is even.  A multiple of 4 runs every Linear on the fp32 GEMM engine; any other even nz (the toy
  * amortizer's Diffusion_Unet at nz = 2, workspace/toy_example/src/diffusion_net.py:63-139 as trained by :241-263 and
  * toy_example.py:209-219) lays out2 out padded to the next multiple of 4 inside the workspace, with zero weights and
- * biases there, and runs the K = nz products around the Fourier embedding as small kernels of their own. */
+ * biases there, and runs the K = nz products around the Fourier embedding as small kernels of their own.
+ * Alignment: the workspace is 16-B aligned (DAMC_ERR_UNSUPPORTED otherwise, on the host before any launch); nothing
+ * else is required.  zt, temb_in, xemb, grad_eps, eps_pred, grad_zt, grad_xemb, every weight of d and every entry of
+ * grads are plain float pointers (4-B aligned): the kernels read and write them one float at a time, but for zt, the A
+ * operand of the z B product, which leaves the grouped float4 kernel for the engine's scalar gather when zt is not 16-B
+ * aligned (as the backward's K = nz / 2 product does when nz / 2 is no multiple of 4).  Any batch >= 1; a batch that is
+ * no multiple of 4 runs every weight and bias gradient (K = batch) on the tiled engine's scalar gather, split over K from
+ * 97 rows on.
+ * Returns, all on the host before any launch: DAMC_ERR_ARG for a descriptor damc_denoiser_train_workspace_bytes gives
+ * 0 for (odd nz or ntemb, a NULL weight, widths that are not Diffusion_UnetA's wiring), batch <= 0 or a NULL zt,
+ * temb_in, xemb, eps_pred, grad_eps or grads; DAMC_ERR_WORKSPACE for a NULL or short workspace. */
 typedef damc_denoiser_t damc_denoiser_train_t;
 typedef struct { /* gradients, same layouts (written, not accumulated; NULL entries are skipped) */
   float* bmat;
@@ -542,8 +552,11 @@ int damc_q_loss_backward(const float* eps, const float* eps_pred, const float* g
 
 /* ------------------------------------------------------- E update (round 5; SURVEY §8f, train_gen_recon.py:233-241)
  * E(z) of _netE (diffusion_net.py:207-223, e's PyTorch-layout w1..b3; w1t / w2t unused) keeping the hidden activations
- * h1, h2 (B, nh) for the backward; energy (B).  Batch and the layer widths multiples of 4, weights 16-B aligned
- * (DAMC_ERR_UNSUPPORTED otherwise: the caller keeps PyTorch). */
+ * h1, h2 (B, nh) for the backward; energy (B).  Batch and the layer widths multiples of 4, a LeakyReLU slope >= 0 (the
+ * backward takes LReLU' from the sign of the saved activation), w1, w2, w3 16-B aligned; the forward's z, h1, h2 and the
+ * backward's workspace 16-B aligned too (the float4 rows of the products).  DAMC_ERR_UNSUPPORTED otherwise (the caller
+ * keeps PyTorch), returned on the host before the first launch: nothing has been written.  A descriptor that is refused
+ * has a workspace size of 0.  Biases, grad_energy, the entries of grads and grad_z need no more than a float's 4 B. */
 typedef struct { /* gradients, PyTorch layouts (written, not accumulated; NULL entries are skipped) */
   float *w1, *b1, *w2, *b2, *w3, *b3;
 } damc_ebm_grads_t;
@@ -558,8 +571,11 @@ int damc_ebm_train_backward(const damc_ebm_t* e, const float* z, const float* h1
 /* ------------------------------------------- Q update: prior embedding (round 6; SURVEY §8f, diffusion_net.py:624-641)
  * Q.prior_emb = Linear(nz, nh) -> LeakyReLU(slope >= 0) -> Linear(nh, nout) (diffusion_net.py:577-581), PyTorch-layout
  * weights; the forward keeps the hidden activation h (B, nh) for the backward.  Replaces the stock modules inside
- * Q.calculate_loss (the mask's prior rows / x None).  Batch and widths multiples of 4, weights 16-B aligned
- * (DAMC_ERR_UNSUPPORTED otherwise: the caller keeps PyTorch). */
+ * Q.calculate_loss (the mask's prior rows / x None).  Batch and widths multiples of 4, slope >= 0, w1 and w2 16-B
+ * aligned; the forward's noise and h, the backward's grad_out and workspace 16-B aligned too (the float4 rows of the
+ * products).  DAMC_ERR_UNSUPPORTED otherwise (the caller keeps PyTorch), returned on the host before the first launch:
+ * nothing has been written.  A descriptor that is refused has a workspace size of 0.  Biases, out and the entries of
+ * grads need no more than a float's 4 B. */
 typedef struct {
   int nz, nh, nout;
   float slope;
