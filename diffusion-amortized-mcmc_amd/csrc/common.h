@@ -89,6 +89,17 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t chain, ui
   }
 }
 
+// The drawn (_ds) entry points: the Philox key lives in device memory (damc_draw_state_t), so a captured launch draws
+// new noise on every replay.  ds != null: seed = ds->seed and the host offset gains ds->counter; ds == null (every
+// entry point that takes a host seed) leaves both as the kernel arguments gave them.  ds is a kernel argument, so the
+// branch and the two loads are wave-uniform; call it once, at the top of the kernel.
+__device__ __forceinline__ void draw_key(const damc_draw_state_t* ds, uint64_t& seed, uint64_t& offset) {
+  if (ds) {
+    seed = ds->seed;
+    offset += ds->counter;
+  }
+}
+
 enum { DAMC_STREAM_POSTERIOR = 0x51, DAMC_STREAM_PRIOR = 0x52, DAMC_STREAM_SWEEP = 0x53 };
 // the guided sweep's per-step prior-embedding noise, keyed (seed, chain_base + row, step k, quad): drawn by the caller
 // (damc_philox_normal), never by a kernel

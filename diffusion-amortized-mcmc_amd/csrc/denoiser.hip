@@ -1561,9 +1561,13 @@ __global__ void transpose_kernel(const float* in, int rows, int cols, float* out
 // the call's per-call record and z, and (team launch) the error word zeroed: a kernel in
 // the stream, not a memset node, so a captured sweep orders it like every other kernel
 __global__ void sweep_setup_kernel(SweepCall c, SweepCall* dst, const float* zt, float* zw, long n, unsigned* zero,
-                                   long nzero, f32x4* s1, long ns1, f32x4* s2, long ns2) {
+                                   long nzero, f32x4* s1, long ns1, f32x4* s2, long ns2, const damc_draw_state_t* ds) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) *dst = c;
+  if (i == 0) {
+    // damc_reverse_sweep_ds: the record takes its key from the device-resident state, read here once per sweep
+    draw_key(ds, c.seed, c.step_offset);
+    *dst = c;
+  }
   // every range is grid-stride: the grid is capped (sweep_setup_grid), so B*nz may exceed the thread count
   const long st = (long)gridDim.x * blockDim.x;
   // a caller's NaN is stored canonical, so a NaN payload can never be the hand-off sentinel (TS_SENT) in the ring
@@ -2630,7 +2634,7 @@ static int stage_hyper(const Stages& st, const float* cx, float* gh, long M) {
 // caller's zt in place; the call's values travel in the kernel arguments
 static int rows_args(const Stages& st, damc::RowsArgs& ra, float* zt, int B, int n, const float* coef, int with_noise,
                      const float* noise, uint64_t seed, uint64_t chain_base, uint64_t step_offset, float* eps_log,
-                     int eps_log_steps) {
+                     int eps_log_steps, const damc_draw_state_t* ds = nullptr) {
   const damc_denoiser_t* d = st.d;
   memset(&ra, 0, sizeof(ra));
   ra.ld = rows_ld(d, ra.b);
@@ -2659,6 +2663,7 @@ static int rows_args(const Stages& st, damc::RowsArgs& ra, float* zt, int B, int
   ra.seed = seed;
   ra.chain_base = chain_base;
   ra.step_offset = step_offset;
+  ra.draws = ds;
   ra.with_noise = with_noise ? 1 : 0;
   return step_table(coef, n, st.s, &ra.tab);
 }
@@ -2673,7 +2678,8 @@ static double rows_flops(const damc_denoiser_t* d, double rows, int n) {
 static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float* zt, int B, int n,
                               const float* temb_in, const float* coef, int with_noise, const float* noise,
                               uint64_t seed, uint64_t chain_base, float* eps_log, int eps_log_steps, void* wsp,
-                              size_t wsb, void* stream, uint64_t step_offset, bool allow_graph) {
+                              size_t wsb, void* stream, uint64_t step_offset, bool allow_graph,
+                              const damc_draw_state_t* ds = nullptr) {
   int rc = validate(d);
   if (rc) return rc;
   if (!xemb || !zt || !temb_in || !coef || B <= 0 || n <= 0) return DAMC_ERR_ARG;
@@ -2699,7 +2705,7 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   if (rows) {
     damc::RowsArgs ra;
     if ((rc = rows_args(st, ra, zt, B, n, coef, with_noise, noise, seed, chain_base, step_offset, eps_log,
-                        eps_log_steps)))
+                        eps_log_steps, ds)))
       return rc;
     ProfScope ps("denoise_chain", rows_flops(d, B, n), s);
     return damc::launch_sweep_rows(ra, s);
@@ -2736,7 +2742,7 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   const long sgrid = std::min<long>(std::max<long>(std::max(nzb, nzero), (ns1 + ns2) / 8), 1L << 16);
   hipLaunchKernelGGL(sweep_setup_kernel, dim3((unsigned)((sgrid + 255) / 256)), dim3(256), 0, s, call, w.call, zt,
                      team ? w.zring : w.z, nzb, reinterpret_cast<unsigned*>(w.err), nzero, reinterpret_cast<f32x4*>(w.ring), ns1,
-                     reinterpret_cast<f32x4*>(w.zring + nzb), ns2);
+                     reinterpret_cast<f32x4*>(w.zring + nzb), ns2, ds);
   DAMC_LAUNCH_CHECK();
   double flops_step = 0;
   for (int j = 0; j < 7; ++j) flops_step += 2.0 * B * 2.0 * d->blocks[j].din * d->blocks[j].dout;
@@ -2767,6 +2773,17 @@ extern "C" int damc_reverse_sweep(const damc_denoiser_t* d, const float* xemb, f
                                   void* wsp, size_t wsb, void* stream) {
   return reverse_sweep_impl(d, xemb, zt, B, n, temb_in, coef, with_noise, noise, seed, chain_base, eps_log,
                             eps_log_steps, wsp, wsb, stream, 0, true);
+}
+
+// the drawn form: seed and counter (added to the sweep's step offset 0) from the device-resident state; the same
+// launches, the state read by sweep_setup_kernel (team, launch chain) or by the row-resident kernel itself
+extern "C" int damc_reverse_sweep_ds(const damc_denoiser_t* d, const float* xemb, float* zt, int B, int n,
+                                     const float* temb_in, const float* coef, int with_noise, const float* noise,
+                                     const damc_draw_state_t* state, uint64_t chain_base, float* eps_log,
+                                     int eps_log_steps, void* wsp, size_t wsb, void* stream) {
+  if (!state) return DAMC_ERR_ARG;
+  return reverse_sweep_impl(d, xemb, zt, B, n, temb_in, coef, with_noise, noise, 0, chain_base, eps_log,
+                            eps_log_steps, wsp, wsb, stream, 0, true, state);
 }
 
 // SURVEY.md §8b names

@@ -28,6 +28,7 @@ struct RowsArgs {
   const float* noise; // injected (n - 1, B, nz) or null (Philox)
   float* eps_log;     // (eps_log_steps, B, nz) or null
   uint64_t seed, chain_base, step_offset;
+  const damc_draw_state_t* draws;  // damc_reverse_sweep_ds: the device-resident key (common.h draw_key), or null
   int with_noise, eps_log_steps;
   // guided sweep only (launch_sweep_rows_guided): the unconditional planes, and the guidance weights 1 + w and w
   const float* gh_u;  // (n, B, ldgh)

@@ -34,7 +34,7 @@ __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<
 // the FINAL epilogue
 template <bool EMB, bool FINAL, bool GUIDED>
 __device__ __forceinline__ void rows_block(const RowsArgs& a, const RowsBlock& b, float* lds, int k, int r0,
-                                           const float* tb) {
+                                           const float* tb, uint64_t seed, uint64_t step_offset) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = lane & 15, q = lane >> 4;
   const int LD = a.ld, niter = b.kp >> 6;
@@ -148,7 +148,7 @@ __device__ __forceinline__ void rows_block(const RowsArgs& a, const RowsBlock& b
               xi = a.noise[((long)noisy_k * a.B + row) * a.nz + c];
             } else {
               float n4[4];
-              philox_normal4(a.seed, a.chain_base + row, a.step_offset + noisy_k, (uint32_t)(c >> 2), DAMC_STREAM_SWEEP,
+              philox_normal4(seed, a.chain_base + row, step_offset + noisy_k, (uint32_t)(c >> 2), DAMC_STREAM_SWEEP,
                              n4);
               xi = pick4(n4, c);
             }
@@ -171,6 +171,8 @@ __global__ __launch_bounds__(RW_THREADS) void sweep_rows_kernel(RowsArgs a) {
   const int r0 = blockIdx.x * (GUIDED ? ROWS_GTM : ROWS_TM);
   const int nz = a.nz, half = nz >> 1, LD = a.ld;
   const int zoff = 2 * half;  // z within X0
+  uint64_t seed = a.seed, step_offset = a.step_offset;
+  draw_key(a.draws, seed, step_offset);
   for (int i = tid; i < ROWS_TM * nz; i += RW_THREADS) {
     const int r = i / nz, c = i - r * nz;
     const int row = GUIDED ? r0 + (r & 7) : r0 + r;
@@ -214,10 +216,10 @@ __global__ __launch_bounds__(RW_THREADS) void sweep_rows_kernel(RowsArgs a) {
       }
     }
     __syncthreads();
-    rows_block<true, false, GUIDED>(a, a.b[0], lds, k, r0, tb);
+    rows_block<true, false, GUIDED>(a, a.b[0], lds, k, r0, tb, seed, step_offset);
 #pragma unroll 1
-    for (int j = 1; j < 6; ++j) rows_block<false, false, GUIDED>(a, a.b[j], lds, k, r0, tb);
-    rows_block<false, true, GUIDED>(a, a.b[6], lds, k, r0, tb);
+    for (int j = 1; j < 6; ++j) rows_block<false, false, GUIDED>(a, a.b[j], lds, k, r0, tb, seed, step_offset);
+    rows_block<false, true, GUIDED>(a, a.b[6], lds, k, r0, tb, seed, step_offset);
   }
   for (int i = tid; i < (GUIDED ? ROWS_GTM : ROWS_TM) * nz; i += RW_THREADS) {
     const int r = i / nz, c = i - r * nz;

@@ -888,10 +888,12 @@ __global__ void q_noise_glue_seeded_kernel(const float* __restrict__ z, int B, i
                                            const float* __restrict__ freqs, int ntemb, uint64_t seed,
                                            uint64_t draw_index, uint64_t chain_base, float* __restrict__ u_out,
                                            float* __restrict__ eps, float* __restrict__ logsnr,
-                                           float* __restrict__ zt, float* __restrict__ temb) {
+                                           float* __restrict__ zt, float* __restrict__ temb,
+                                           const damc_draw_state_t* ds) {
   const int W = max(nz, ntemb);
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)B * W) return;
+  draw_key(ds, seed, draw_index);
   const int n = (int)(i / W), j = (int)(i - (long)n * W);
   const uint64_t chain = chain_base + (uint64_t)n;
   const float un = u01_halfopen(philox_block(seed, chain, draw_index, 0u, DAMC_STREAM_QU).v[0]);
@@ -941,17 +943,35 @@ extern "C" int damc_q_noise_glue(const float* u, const float* z, const float* ep
   return (int)hipGetLastError();
 }
 
-extern "C" int damc_q_noise_glue_seeded(const float* z, int batch, int nz, float logsnr_min, float logsnr_max,
-                                        const float* freqs, int ntemb, uint64_t seed, uint64_t draw_index,
-                                        uint64_t chain_base, float* u, float* eps, float* logsnr, float* zt,
-                                        float* temb_in, void* stream) {
+static int q_noise_glue_seeded_impl(const float* z, int batch, int nz, float logsnr_min, float logsnr_max,
+                                    const float* freqs, int ntemb, uint64_t seed, uint64_t draw_index,
+                                    uint64_t chain_base, float* u, float* eps, float* logsnr, float* zt, float* temb_in,
+                                    void* stream, const damc_draw_state_t* ds) {
   if (!z || !eps || !freqs || !zt || !temb_in || batch <= 0 || nz <= 0 || ntemb < 2 || ntemb % 2)
     return DAMC_ERR_ARG;
   const long n = (long)batch * std::max(nz, ntemb);
   hipLaunchKernelGGL(damc::q_noise_glue_seeded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      as_stream(stream), z, batch, nz, logsnr_min, logsnr_max, freqs, ntemb, seed, draw_index,
-                     chain_base, u, eps, logsnr, zt, temb_in);
+                     chain_base, u, eps, logsnr, zt, temb_in, ds);
   return (int)hipGetLastError();
+}
+
+extern "C" int damc_q_noise_glue_seeded(const float* z, int batch, int nz, float logsnr_min, float logsnr_max,
+                                        const float* freqs, int ntemb, uint64_t seed, uint64_t draw_index,
+                                        uint64_t chain_base, float* u, float* eps, float* logsnr, float* zt,
+                                        float* temb_in, void* stream) {
+  return q_noise_glue_seeded_impl(z, batch, nz, logsnr_min, logsnr_max, freqs, ntemb, seed, draw_index, chain_base, u,
+                                  eps, logsnr, zt, temb_in, stream, nullptr);
+}
+
+// the drawn form: seed and counter from the device-resident state (common.h draw_key); the same kernel
+extern "C" int damc_q_noise_glue_seeded_ds(const float* z, int batch, int nz, float logsnr_min, float logsnr_max,
+                                           const float* freqs, int ntemb, const damc_draw_state_t* state,
+                                           uint64_t draw_index, uint64_t chain_base, float* u, float* eps,
+                                           float* logsnr, float* zt, float* temb_in, void* stream) {
+  if (!state) return DAMC_ERR_ARG;
+  return q_noise_glue_seeded_impl(z, batch, nz, logsnr_min, logsnr_max, freqs, ntemb, 0, draw_index, chain_base, u, eps,
+                                  logsnr, zt, temb_in, stream, state);
 }
 
 extern "C" int damc_q_loss_forward(const float* eps, const float* eps_pred, int batch, int nz, float* loss,

@@ -172,8 +172,9 @@ __global__ __launch_bounds__(EBM_THREADS) void posterior_update_kernel(damc_ebm_
                                                                 int nslab, long slab_stride, int B, int nz, float c1,
                                                                 float step, int with_noise, const float* noise,
                                                                 uint64_t seed, uint64_t step_idx, uint64_t chain_base,
-                                                                float* diag) {
+                                                                float* diag, const damc_draw_state_t* ds) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  draw_key(ds, seed, step_idx);
   const int nh = use_ebm ? e.nh : 0;
   EbmSmem s = ebm_carve(smem, R, nz, nh);
   const int row0 = blockIdx.x * R;
@@ -227,8 +228,10 @@ __global__ __launch_bounds__(EBM_THREADS) void posterior_update_kernel(damc_ebm_
 template <int R>
 __global__ __launch_bounds__(EBM_THREADS) void prior_chain_kernel(damc_ebm_t e, float* z, int B, int n_steps, float c1, float step,
                                                            int with_noise, const float* noise, uint64_t seed,
-                                                           uint64_t step_offset, uint64_t chain_base, float* diag) {
+                                                           uint64_t step_offset, uint64_t chain_base, float* diag,
+                                                           const damc_draw_state_t* ds) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  draw_key(ds, seed, step_offset);
   const int nz = e.nz;
   EbmSmem s = ebm_carve(smem, R, nz, e.nh);
   __shared__ float en_rows[R];
@@ -291,9 +294,11 @@ __global__ __launch_bounds__(EBM_THREADS) void ebm_energy_grad_kernel(damc_ebm_t
 }
 
 __global__ void z_update_kernel(float* z, const float* g, long n, int nz, float c1, float step, int with_noise,
-                                const float* noise, uint64_t seed, uint64_t step_idx, uint64_t chain_base) {
+                                const float* noise, uint64_t seed, uint64_t step_idx, uint64_t chain_base,
+                                const damc_draw_state_t* ds) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  draw_key(ds, seed, step_idx);
   const long r = i / nz;
   const int c = (int)(i - r * nz);
   const float zv = z[i];
@@ -306,10 +311,11 @@ __global__ void z_update_kernel(float* z, const float* g, long n, int nz, float 
 }
 
 __global__ void philox_normal_kernel(float* out, int n_steps, int B, int nz, uint64_t seed, uint64_t step_offset,
-                                     uint64_t chain_base, uint32_t stream_id) {
+                                     uint64_t chain_base, uint32_t stream_id, const damc_draw_state_t* ds) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long n = (long)n_steps * B * nz;
   if (i >= n) return;
+  draw_key(ds, seed, step_offset);
   const long st = i / ((long)B * nz);
   const long rem = i - st * B * nz;
   const long r = rem / nz;
@@ -321,12 +327,17 @@ __global__ void philox_normal_kernel(float* out, int n_steps, int B, int nz, uin
 
 // one U[0, 1) value per (step, row): word 0 of the block philox_normal4 draws for quad 0 of that (chain, step)
 __global__ void philox_uniform_kernel(float* out, int n_steps, int B, uint64_t seed, uint64_t step_offset,
-                                      uint64_t chain_base, uint32_t stream_id) {
+                                      uint64_t chain_base, uint32_t stream_id, const damc_draw_state_t* ds) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)n_steps * B) return;
+  draw_key(ds, seed, step_offset);
   const long st = i / B, r = i - st * B;
   out[i] = u01_halfopen(philox_block(seed, chain_base + r, step_offset + st, 0u, stream_id).v[0]);
 }
+
+// damc_draw_state_advance: counter += delta, stream-ordered like every launch, so a captured graph that ends with it
+// draws from the next indices on its next replay
+__global__ void draw_state_advance_kernel(damc_draw_state_t* st, uint64_t delta) { st->counter += delta; }
 
 // ================================================================================================
 // Register-resident EBM (the default for nh <= 208, nz <= 128: _netE at every BASELINE config).
@@ -408,6 +419,7 @@ struct EbArgs {
   int with_noise;
   const float* noise;  // injected: PRIOR (n_steps, B, nz), POSTERIOR (B, nz)
   uint64_t seed, step_offset, chain_base;
+  const damc_draw_state_t* draws;  // the drawn entry points' device key (draw_key), or null
   float* diag;         // PRIOR: (n_steps, 2) {sum E, |z|^2/2};  POSTERIOR: (4) {sum E, -, |z|^2/2, mean grad}
   // POSTERIOR with nslab > 1: glik is the sum of nslab split-K slabs (slab k at slabs + k * slab_stride), added in
   // slab_sum4_kernel's fixed order (16 groups of every 16th slab, then the groups in order), so the fused sum is
@@ -437,6 +449,8 @@ __global__ __launch_bounds__(EB_THREADS) void ebm_reg_kernel(EbArgs a) {
   const float sl = e.slope;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int chain = blockIdx.x;
+  uint64_t seed = a.seed, step_offset = a.step_offset;
+  draw_key(a.draws, seed, step_offset);
   __shared__ float zs[64 * EB_K1];
   __shared__ float xs[64 * EB_K1];  // this step's noise
   __shared__ float h1s[EB_WAVES * EB_RW];
@@ -496,9 +510,9 @@ __global__ __launch_bounds__(EB_THREADS) void ebm_reg_kernel(EbArgs a) {
       const int c = tid - (EB_WAVES - 2) * 64;
       if (c < nz) {
         xs[c] = MODE == EB_PRIOR
-                    ? noise_at(a.noise, ((long)it * a.B + chain) * nz + c, 1, a.seed, a.chain_base + chain,
-                               a.step_offset + it, c, DAMC_STREAM_PRIOR)
-                    : noise_at(a.noise, (long)chain * nz + c, 1, a.seed, a.chain_base + chain, a.step_offset, c,
+                    ? noise_at(a.noise, ((long)it * a.B + chain) * nz + c, 1, seed, a.chain_base + chain,
+                               step_offset + it, c, DAMC_STREAM_PRIOR)
+                    : noise_at(a.noise, (long)chain * nz + c, 1, seed, a.chain_base + chain, step_offset, c,
                                DAMC_STREAM_POSTERIOR);
       }
     }
@@ -687,6 +701,8 @@ __global__ __launch_bounds__(EM_THREADS) void prior_chain_mfma_kernel(EbArgs a) 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = lane & 15, q = lane >> 4;
   const int r0 = blockIdx.x * EM_ROWS;
+  uint64_t seed = a.seed, step_offset = a.step_offset;
+  draw_key(a.draws, seed, step_offset);
   __shared__ __attribute__((aligned(16))) float zs[EM_ROWS * EM_LD];
   __shared__ __attribute__((aligned(16))) float h1[EM_ROWS * EM_LD];  // lrelu(a1), then g1
   __shared__ __attribute__((aligned(16))) float a1s[EM_ROWS * EM_LD];
@@ -755,8 +771,8 @@ __global__ __launch_bounds__(EM_THREADS) void prior_chain_mfma_kernel(EbArgs a) 
           zsq += zv * zv;
           float zn = sub_rn(zv, mul_rn(a.c1, g));
           if (a.with_noise) {
-            const float xi = noise_at(a.noise, ((long)it * a.B + row) * nz + c, 1, a.seed, a.chain_base + row,
-                                      a.step_offset + it, c, DAMC_STREAM_PRIOR);
+            const float xi = noise_at(a.noise, ((long)it * a.B + row) * nz + c, 1, seed, a.chain_base + row,
+                                      step_offset + it, c, DAMC_STREAM_PRIOR);
             zn = add_rn(zn, mul_rn(a.step, xi));
           }
           zs[(4 * q + r) * EM_LD + c] = zn;
@@ -810,7 +826,7 @@ bool damc_posterior_update_fusable(const damc_ebm_t* e, int nz) { return e && e-
 int damc_launch_posterior_update(const damc_ebm_t* e, float* z, const float* slabs, int nslab, long slab_stride, int B,
                                  int nz, double step, int with_noise, const float* noise, uint64_t seed,
                                  uint64_t step_idx, uint64_t chain_base, float* diag, hipStream_t s,
-                                 unsigned short* z3, bool* wrote_z3) {
+                                 unsigned short* z3, bool* wrote_z3, const damc_draw_state_t* ds) {
   if (wrote_z3) *wrote_z3 = false;
   damc_ebm_t ev{};
   int use_ebm = 0;
@@ -837,6 +853,7 @@ int damc_launch_posterior_update(const damc_ebm_t* e, float* z, const float* sla
     a.noise = noise;
     a.seed = seed;
     a.step_offset = step_idx;
+    a.draws = ds;
     a.chain_base = chain_base;
     a.diag = diag;
     ProfScope ps("posterior_update", 4.0 * B * ((double)nz * ev.nh + (double)ev.nh * ev.nh), s);
@@ -847,7 +864,8 @@ int damc_launch_posterior_update(const damc_ebm_t* e, float* z, const float* sla
   const size_t sm = ebm_smem_floats(RU, nz, use_ebm ? ev.nh : 0) * sizeof(float);
   ProfScope ps("posterior_update", 0.0, s);
   hipLaunchKernelGGL((posterior_update_kernel<RU>), dim3((B + RU - 1) / RU), dim3(EBM_THREADS), sm, s, ev, use_ebm, z, slabs,
-                     nslab, slab_stride, B, nz, c1, (float)step, with_noise, noise, seed, step_idx, chain_base, diag);
+                     nslab, slab_stride, B, nz, c1, (float)step, with_noise, noise, seed, step_idx, chain_base, diag,
+                     ds);
   return (int)hipGetLastError();
 }
 
@@ -866,7 +884,7 @@ extern "C" int damc_ebm_mfma_min_chains(void) {
 // engine: 0 = by batch size (MFMA from DAMC_EBM_MFMA_MIN_B chains up), 1 = register-resident VALU, 2 = MFMA
 static int prior_langevin_impl(const damc_ebm_t* e, float* z, int B, int n_steps, double step, int with_noise,
                                const float* noise, uint64_t seed, uint64_t step_offset, uint64_t chain_base,
-                               float* diag, void* stream, int engine) {
+                               float* diag, void* stream, int engine, const damc_draw_state_t* ds = nullptr) {
   if (!e || !z || B <= 0 || n_steps < 0) return DAMC_ERR_ARG;
   if (!e->w1t || !e->w2t) return DAMC_ERR_ARG;
   hipStream_t s = as_stream(stream);
@@ -887,6 +905,7 @@ static int prior_langevin_impl(const damc_ebm_t* e, float* z, int B, int n_steps
     a.noise = noise;
     a.seed = seed;
     a.step_offset = step_offset;
+    a.draws = ds;
     a.chain_base = chain_base;
     a.diag = diag;
     ProfScope ps("prior_chain_mfma", 4.0 * (double)B * n_steps * ((double)e->nz * e->nh + (double)e->nh * e->nh), s);
@@ -905,6 +924,7 @@ static int prior_langevin_impl(const damc_ebm_t* e, float* z, int B, int n_steps
     a.noise = noise;
     a.seed = seed;
     a.step_offset = step_offset;
+    a.draws = ds;
     a.chain_base = chain_base;
     a.diag = diag;
     ProfScope ps("prior_chain", 4.0 * (double)B * n_steps * ((double)e->nz * e->nh + (double)e->nh * e->nh), s);
@@ -915,7 +935,7 @@ static int prior_langevin_impl(const damc_ebm_t* e, float* z, int B, int n_steps
   const size_t sm = ebm_smem_floats(RP, e->nz, e->nh) * sizeof(float);
   ProfScope ps("prior_chain", 4.0 * (double)B * n_steps * ((double)e->nz * e->nh + (double)e->nh * e->nh), s);
   hipLaunchKernelGGL((prior_chain_kernel<RP>), dim3((B + RP - 1) / RP), dim3(EBM_THREADS), sm, s, *e, z, B, n_steps, c1, (float)step,
-                     with_noise, noise, seed, step_offset, chain_base, diag);
+                     with_noise, noise, seed, step_offset, chain_base, diag, ds);
   return (int)hipGetLastError();
 }
 
@@ -931,6 +951,21 @@ extern "C" int damc_prior_langevin_engine(const damc_ebm_t* e, float* z, int B, 
   if (engine < 0 || engine > 2) return DAMC_ERR_ARG;
   return prior_langevin_impl(e, z, B, n_steps, step, with_noise, noise, seed, step_offset, chain_base, diag, stream,
                              engine);
+}
+
+// the drawn form: seed and counter from the device-resident state (common.h draw_key); the same kernels
+extern "C" int damc_prior_langevin_ds(const damc_ebm_t* e, float* z, int B, int n_steps, double step, int with_noise,
+                                      const float* noise, const damc_draw_state_t* state, uint64_t step_offset,
+                                      uint64_t chain_base, float* diag, int engine, void* stream) {
+  if (!state || engine < 0 || engine > 2) return DAMC_ERR_ARG;
+  return prior_langevin_impl(e, z, B, n_steps, step, with_noise, noise, 0, step_offset, chain_base, diag, stream,
+                             engine, state);
+}
+
+extern "C" int damc_draw_state_advance(damc_draw_state_t* state, uint64_t delta, void* stream) {
+  if (!state) return DAMC_ERR_ARG;
+  hipLaunchKernelGGL(draw_state_advance_kernel, dim3(1), dim3(1), 0, as_stream(stream), state, delta);
+  return (int)hipGetLastError();
 }
 
 extern "C" int damc_ebm_energy_grad(const damc_ebm_t* e, const float* z, int B, float* energy, float* grad,
@@ -953,32 +988,67 @@ extern "C" int damc_ebm_energy_grad(const damc_ebm_t* e, const float* z, int B, 
   return (int)hipGetLastError();
 }
 
-extern "C" int damc_z_update(float* z, const float* g, int B, int nz, double step, int with_noise, const float* noise,
-                             uint64_t seed, uint64_t step_index, uint64_t chain_base, void* stream) {
+static int z_update_impl(float* z, const float* g, int B, int nz, double step, int with_noise, const float* noise,
+                         uint64_t seed, uint64_t step_index, uint64_t chain_base, void* stream,
+                         const damc_draw_state_t* ds) {
   if (!z || !g || B <= 0 || nz <= 0) return DAMC_ERR_ARG;
   const long n = (long)B * nz;
   const float c1 = (float)(0.5 * step * step);  // float32(0.5 * s * s), the reference's scalar
   hipLaunchKernelGGL(z_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), z, g, n, nz, c1,
-                     (float)step, with_noise, noise, seed, step_index, chain_base);
+                     (float)step, with_noise, noise, seed, step_index, chain_base, ds);
+  return (int)hipGetLastError();
+}
+
+extern "C" int damc_z_update(float* z, const float* g, int B, int nz, double step, int with_noise, const float* noise,
+                             uint64_t seed, uint64_t step_index, uint64_t chain_base, void* stream) {
+  return z_update_impl(z, g, B, nz, step, with_noise, noise, seed, step_index, chain_base, stream, nullptr);
+}
+
+extern "C" int damc_z_update_ds(float* z, const float* g, int B, int nz, double step, int with_noise,
+                                const float* noise, const damc_draw_state_t* state, uint64_t step_index,
+                                uint64_t chain_base, void* stream) {
+  if (!state) return DAMC_ERR_ARG;
+  return z_update_impl(z, g, B, nz, step, with_noise, noise, 0, step_index, chain_base, stream, state);
+}
+
+static int philox_normal_impl(float* out, int n_steps, int B, int nz, uint64_t seed, uint64_t step_offset,
+                              uint64_t chain_base, uint32_t stream_id, void* stream, const damc_draw_state_t* ds) {
+  const long n = (long)n_steps * B * nz;
+  if (!out || n <= 0) return DAMC_ERR_ARG;
+  hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), out,
+                     n_steps, B, nz, seed, step_offset, chain_base, stream_id, ds);
   return (int)hipGetLastError();
 }
 
 extern "C" int damc_philox_normal(float* out, int n_steps, int B, int nz, uint64_t seed, uint64_t step_offset,
                                   uint64_t chain_base, uint32_t stream_id, void* stream) {
-  const long n = (long)n_steps * B * nz;
-  if (!out || n <= 0) return DAMC_ERR_ARG;
-  hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), out,
-                     n_steps, B, nz, seed, step_offset, chain_base, stream_id);
+  return philox_normal_impl(out, n_steps, B, nz, seed, step_offset, chain_base, stream_id, stream, nullptr);
+}
+
+extern "C" int damc_philox_normal_ds(float* out, int n_steps, int B, int nz, const damc_draw_state_t* state,
+                                     uint64_t step_offset, uint64_t chain_base, uint32_t stream_id, void* stream) {
+  if (!state) return DAMC_ERR_ARG;
+  return philox_normal_impl(out, n_steps, B, nz, 0, step_offset, chain_base, stream_id, stream, state);
+}
+
+static int philox_uniform_impl(float* out, int n_steps, int B, uint64_t seed, uint64_t step_offset,
+                               uint64_t chain_base, uint32_t stream_id, void* stream, const damc_draw_state_t* ds) {
+  if (!out || n_steps <= 0 || B <= 0) return DAMC_ERR_ARG;
+  const long n = (long)n_steps * B;
+  hipLaunchKernelGGL(philox_uniform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), out,
+                     n_steps, B, seed, step_offset, chain_base, stream_id, ds);
   return (int)hipGetLastError();
 }
 
 extern "C" int damc_philox_uniform(float* out, int n_steps, int B, uint64_t seed, uint64_t step_offset,
                                    uint64_t chain_base, uint32_t stream_id, void* stream) {
-  if (!out || n_steps <= 0 || B <= 0) return DAMC_ERR_ARG;
-  const long n = (long)n_steps * B;
-  hipLaunchKernelGGL(philox_uniform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), out,
-                     n_steps, B, seed, step_offset, chain_base, stream_id);
-  return (int)hipGetLastError();
+  return philox_uniform_impl(out, n_steps, B, seed, step_offset, chain_base, stream_id, stream, nullptr);
+}
+
+extern "C" int damc_philox_uniform_ds(float* out, int n_steps, int B, const damc_draw_state_t* state,
+                                      uint64_t step_offset, uint64_t chain_base, uint32_t stream_id, void* stream) {
+  if (!state) return DAMC_ERR_ARG;
+  return philox_uniform_impl(out, n_steps, B, 0, step_offset, chain_base, stream_id, stream, state);
 }
 
 // ---- packing: w1t = w1^T (nz, nh), w2t = w2^T (nh, nh)

@@ -24,7 +24,8 @@ using damc::smallc_ntile;
 int damc_launch_posterior_update(const damc_ebm_t* e, float* z, const float* slabs, int nslab, long slab_stride, int B,
                                  int nz, double step, int with_noise, const float* noise, uint64_t seed,
                                  uint64_t step_idx, uint64_t chain_base, float* diag, hipStream_t s,
-                                 unsigned short* z3 = nullptr, bool* wrote_z3 = nullptr);
+                                 unsigned short* z3 = nullptr, bool* wrote_z3 = nullptr,
+                                 const damc_draw_state_t* ds = nullptr);
 bool damc_posterior_update_fusable(const damc_ebm_t* e, int nz);
 
 namespace {
@@ -1106,10 +1107,11 @@ extern "C" int damc_convT_dgrad(const damc_layer_t* L, const float* gout, int B,
                            "upconv_dgrad", conv_flops(*L, B), s);
 }
 
-extern "C" int damc_posterior_langevin(const damc_generator_t* g, const damc_ebm_t* ebm, float* z, const float* x,
-                                       int B, int n_steps, double sigma, double step, int with_noise, const float* noise,
-                                       uint64_t seed, uint64_t step_offset, uint64_t chain_base, float* diag,
-                                       void* wsp, size_t wsb, void* stream) {
+// ds: the drawn form's device-resident key (the update kernel reads it, common.h draw_key), null for a host seed
+static int posterior_langevin_impl(const damc_generator_t* g, const damc_ebm_t* ebm, float* z, const float* x, int B,
+                                   int n_steps, double sigma, double step, int with_noise, const float* noise,
+                                   uint64_t seed, uint64_t step_offset, uint64_t chain_base, float* diag, void* wsp,
+                                   size_t wsb, void* stream, const damc_draw_state_t* ds) {
   Workspace ws;
   int rc = setup_ws(g, B, wsp, wsb, &ws);
   if (rc) return rc;
@@ -1149,11 +1151,28 @@ extern "C" int damc_posterior_langevin(const damc_generator_t* g, const damc_ebm
     bool wrote = false;
     rc = damc_launch_posterior_update(ebm, z, f ? ws.slabs : ws.glik, f ? ws.nslab : 1, n, B, g->nz, step,
                                       with_noise, nz_i, seed, step_offset + i, chain_base, dg, s,
-                                      (f && z3_use) ? ws.z3 : nullptr, &wrote);
+                                      (f && z3_use) ? ws.z3 : nullptr, &wrote, ds);
     if (rc) return rc;
     z3_ready = wrote;
   }
   return 0;
+}
+
+extern "C" int damc_posterior_langevin(const damc_generator_t* g, const damc_ebm_t* ebm, float* z, const float* x,
+                                       int B, int n_steps, double sigma, double step, int with_noise, const float* noise,
+                                       uint64_t seed, uint64_t step_offset, uint64_t chain_base, float* diag,
+                                       void* wsp, size_t wsb, void* stream) {
+  return posterior_langevin_impl(g, ebm, z, x, B, n_steps, sigma, step, with_noise, noise, seed, step_offset,
+                                 chain_base, diag, wsp, wsb, stream, nullptr);
+}
+
+extern "C" int damc_posterior_langevin_ds(const damc_generator_t* g, const damc_ebm_t* ebm, float* z, const float* x,
+                                          int B, int n_steps, double sigma, double step, int with_noise,
+                                          const float* noise, const damc_draw_state_t* state, uint64_t step_offset,
+                                          uint64_t chain_base, float* diag, void* wsp, size_t wsb, void* stream) {
+  if (!state) return DAMC_ERR_ARG;
+  return posterior_langevin_impl(g, ebm, z, x, B, n_steps, sigma, step, with_noise, noise, 0, step_offset, chain_base,
+                                 diag, wsp, wsb, stream, state);
 }
 
 // ------------------------------------------------------------------------------------ training (G update)

@@ -42,7 +42,8 @@ struct AdamPtrs {
   float* m[DAMC_ADAM_MAX_TENSORS];
   float* v[DAMC_ADAM_MAX_TENSORS];
 };
-static_assert(sizeof(AdamPtrs) + sizeof(damc_adam_hparams_t) + 64 <= 4096, "kernel argument block");
+static_assert(sizeof(AdamPtrs) + sizeof(damc_adam_capturable_t) + 3 * 8 + 64 <= 4096 &&
+              sizeof(AdamPtrs) + sizeof(damc_adam_hparams_t) + 64 <= 4096, "kernel argument block");
 
 constexpr int kThreads = 256;
 
@@ -69,9 +70,10 @@ __device__ __forceinline__ void adam_elem(float& p, float& g, float& m, float& v
   p = fmaf(h.neg_step_size, m / s, p);
 }
 
+// one chunk (blockIdx.x) of the step, shared by the host-scalar and the capturable kernel
 template <bool CLIP>
-__global__ __launch_bounds__(kThreads) void adam_kernel(const AdamChunk* __restrict__ chunks, AdamPtrs t,
-                                                        damc_adam_hparams_t h, const float* __restrict__ clip) {
+__device__ __forceinline__ void adam_chunk(const AdamChunk* __restrict__ chunks, const AdamPtrs& t,
+                                           const damc_adam_hparams_t& h, const float* __restrict__ clip) {
   const AdamChunk c = chunks[blockIdx.x];
   float* P = t.p[c.tensor] + c.off;
   float* G = t.g[c.tensor] + c.off;
@@ -110,6 +112,48 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(const AdamChunk* __restr
     V[i] = v;
     if (CLIP) G[i] = g;
   }
+}
+
+template <bool CLIP>
+__global__ __launch_bounds__(kThreads) void adam_kernel(const AdamChunk* __restrict__ chunks, AdamPtrs t,
+                                                        damc_adam_hparams_t h, const float* __restrict__ clip) {
+  adam_chunk<CLIP>(chunks, t, h, clip);
+}
+
+// damc_adam_step_capturable: the same update with the step count (and optionally lr) read from device memory, so a
+// captured launch steps on with every replay.  Thread 0 evaluates what the caller of damc_adam_step evaluates on the
+// host (1 - beta^t, sqrt(1 - beta2^t), lr / (1 - beta1^t), 1 - lr wd: in double, rounded to fp32 once) and the
+// block shares it through LDS; the element arithmetic is adam_elem's.
+__global__ void adam_step_count_kernel(float* step) { *step += 1.0f; }
+
+template <bool CLIP>
+__global__ __launch_bounds__(kThreads) void adam_capturable_kernel(const AdamChunk* __restrict__ chunks, AdamPtrs t,
+                                                                   damc_adam_capturable_t hc,
+                                                                   const float* __restrict__ step,
+                                                                   const float* __restrict__ lr_dev,
+                                                                   const float* __restrict__ clip) {
+  __shared__ damc_adam_hparams_t hs;
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    const double tstep = (double)step[0];
+    const double lr = lr_dev ? (double)lr_dev[0] : hc.lr;
+    const double bc1 = 1.0 - pow(hc.beta1, tstep);
+    const double bc2 = 1.0 - pow(hc.beta2, tstep);
+    damc_adam_hparams_t h;
+    h.neg_step_size = (float)((lr / bc1) * -1.0);
+    h.one_minus_beta1 = (float)(1.0 - hc.beta1);
+    h.beta2 = (float)hc.beta2;
+    h.one_minus_beta2 = (float)(1.0 - hc.beta2);
+    h.bc2_sqrt = (float)sqrt(bc2);
+    h.eps = (float)hc.eps;
+    h.decoupled = hc.decoupled;
+    h.weight_decay = hc.decoupled ? 0.f : (float)hc.weight_decay;
+    h.decay_mul = hc.decoupled ? (float)(1.0 - lr * hc.weight_decay) : 1.f;
+    hs = h;
+  }
+  __syncthreads();
+  const damc_adam_hparams_t h = hs;
+  adam_chunk<CLIP>(chunks, t, h, clip);
 }
 
 // fixed-order block sum of 256 per-thread values (wave butterflies in a fixed pattern, then 4 waves)
@@ -334,6 +378,28 @@ int damc_adam_step(const void* dev_chunks, int nchunks, float* const* params, fl
     adam_kernel<true><<<nchunks, kThreads, 0, as_stream(stream)>>>(ch, t, *hp, clip);
   else
     adam_kernel<false><<<nchunks, kThreads, 0, as_stream(stream)>>>(ch, t, *hp, nullptr);
+  DAMC_LAUNCH_CHECK();
+  return 0;
+}
+
+int damc_adam_step_capturable(const void* dev_chunks, int nchunks, float* const* params, float* const* grads,
+                              float* const* exp_avgs, float* const* exp_avg_sqs, int ntensors,
+                              const damc_adam_capturable_t* hp, float* step, int advance, const float* lr,
+                              const float* clip, void* stream) {
+  AdamPtrs t;
+  DAMC_REQUIRE(dev_chunks && hp && step && nchunks >= 0 && fill(params, ntensors, t.p) && fill(grads, ntensors, t.g) &&
+               fill(exp_avgs, ntensors, t.m) && fill(exp_avg_sqs, ntensors, t.v));
+  hipStream_t s = as_stream(stream);
+  if (advance) {
+    adam_step_count_kernel<<<1, 1, 0, s>>>(step);
+    DAMC_LAUNCH_CHECK();
+  }
+  if (nchunks == 0) return 0;
+  const AdamChunk* ch = static_cast<const AdamChunk*>(dev_chunks);
+  if (clip)
+    adam_capturable_kernel<true><<<nchunks, kThreads, 0, s>>>(ch, t, *hp, step, lr, clip);
+  else
+    adam_capturable_kernel<false><<<nchunks, kThreads, 0, s>>>(ch, t, *hp, step, lr, nullptr);
   DAMC_LAUNCH_CHECK();
   return 0;
 }

@@ -11,7 +11,7 @@ __all__ = ["DamcError", "lib", "LIB_PATH", "EXPORTED_SYMBOLS", "synth"]
 
 def __getattr__(name):
     # lazy: torch-dependent modules load on first use
-    if name in ("langevin", "plans", "amortizer", "dist", "anomaly"):
+    if name in ("langevin", "plans", "amortizer", "dist", "anomaly", "graphs"):
         import importlib
 
         return importlib.import_module("." + name, __name__)

@@ -150,6 +150,11 @@ class AdamHparams(ctypes.Structure):
                 ("weight_decay", ctypes.c_float), ("decay_mul", ctypes.c_float), ("decoupled", ctypes.c_int)]
 
 
+class AdamCapturable(ctypes.Structure):  # damc_adam_capturable_t
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("decoupled", ctypes.c_int)]
+
+
 ADAM_CHUNK = 8192
 ADAM_MAX_TENSORS = 96
 
@@ -264,6 +269,18 @@ _SIGS = {
     "damc_grad_scale": (_I, [_P, _I, _P, _I, _P, _P]),
     "damc_grad_pack": (_I, [_P, _I, _P, ctypes.POINTER(ctypes.c_longlong), _I, _F, _P, _P]),
     "damc_adam_step": (_I, [_P, _I, _P, _P, _P, _P, _I, ctypes.POINTER(AdamHparams), _P, _P]),
+    "damc_adam_step_capturable": (_I, [_P, _I, _P, _P, _P, _P, _I, ctypes.POINTER(AdamCapturable), _P, _I, _P, _P, _P]),
+    # the drawn variants: a damc_draw_state_t* (device memory) where the seeded entry point takes its uint64 seed
+    "damc_draw_state_advance": (_I, [_P, _U64, _P]),
+    "damc_posterior_langevin_ds": (_I, [ctypes.POINTER(Generator), ctypes.POINTER(Ebm), _P, _P, _I, _I, _D, _D, _I, _P,
+                                        _P, _U64, _U64, _P, _P, _SZ, _P]),
+    "damc_prior_langevin_ds": (_I, [ctypes.POINTER(Ebm), _P, _I, _I, _D, _I, _P, _P, _U64, _U64, _P, _I, _P]),
+    "damc_z_update_ds": (_I, [_P, _P, _I, _I, _D, _I, _P, _P, _U64, _U64, _P]),
+    "damc_philox_normal_ds": (_I, [_P, _I, _I, _I, _P, _U64, _U64, ctypes.c_uint32, _P]),
+    "damc_philox_uniform_ds": (_I, [_P, _I, _I, _P, _U64, _U64, ctypes.c_uint32, _P]),
+    "damc_reverse_sweep_ds": (_I, [ctypes.POINTER(Denoiser), _P, _P, _I, _I, _P, _P, _I, _P, _P, _U64, _P, _I, _P,
+                                   _SZ, _P]),
+    "damc_q_noise_glue_seeded_ds": (_I, [_P, _I, _I, _F, _F, _P, _I, _P, _U64, _U64, _P, _P, _P, _P, _P, _P]),
     "damc_specnorm_workspace_bytes": (_SZ, [ctypes.POINTER(SpecNormLayer), _I]),
     "damc_specnorm_forward": (_I, [ctypes.POINTER(SpecNormLayer), _I, _I, _P, _SZ, _P]),
     "damc_specnorm_backward": (_I, [ctypes.POINTER(SpecNormLayer), _I, ctypes.POINTER(ctypes.c_void_p), _P, _SZ, _P]),

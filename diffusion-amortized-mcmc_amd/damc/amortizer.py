@@ -340,8 +340,15 @@ def prior_embedding(Q, noise):
     return out
 
 
-def reverse_sweep(Q, xemb, zt, noise=None, seed=None, chain_base=0, eps_log_steps=0, with_noise=None):
-    """In-place latent reverse sweep on zt (B, nz); returns eps of the first eps_log_steps steps."""
+def reverse_sweep(Q, xemb, zt, noise=None, seed=None, chain_base=0, eps_log_steps=0, with_noise=None, draws=None):
+    """In-place latent reverse sweep on zt (B, nz); returns eps of the first eps_log_steps steps.
+
+    draws (a damc.graphs.DrawState, instead of seed): the sweep's Philox key is read on the device
+    (damc_reverse_sweep_ds), bitwise the seeded sweep with seed = the state's and its noisy step k at index counter + k;
+    the counter is advanced by n_interval after the sweep is enqueued, so a captured sweep draws anew per replay."""
+    from .graphs import exclusive
+
+    exclusive(seed, draws, "reverse_sweep")
     dev = zt.device
     plan = _DEN.get(Q.p)
     if plan is None:
@@ -355,10 +362,17 @@ def reverse_sweep(Q, xemb, zt, noise=None, seed=None, chain_base=0, eps_log_step
     with_noise = bool(Q.with_noise) if with_noise is None else bool(with_noise)
     if noise is not None:
         noise = noise.to(device=dev, dtype=torch.float32).contiguous()
-    if seed is None:
+    if seed is None and draws is None:
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if with_noise and noise is None else 0
     xemb = xemb.to(dtype=torch.float32).contiguous()
     eps_log = torch.empty(max(eps_log_steps, 1), B, plan.nz, dtype=torch.float32, device=dev) if eps_log_steps else None
+    if draws is not None:
+        check(L.damc_reverse_sweep_ds(ctypes.byref(d), ptr(xemb), ptr(zt), B, n, ptr(temb_d),
+                                      coef_h.numpy().ctypes.data_as(ctypes.c_void_p), int(with_noise), ptr(noise),
+                                      draws.ptr(), chain_base, ptr(eps_log), int(eps_log_steps), ptr(ws), nbytes,
+                                      _lib.stream_ptr(dev)), "damc_reverse_sweep_ds")
+        draws.advance(n)
+        return eps_log
     check(L.damc_reverse_sweep(ctypes.byref(d), ptr(xemb), ptr(zt), B, n, ptr(temb_d),
                                coef_h.numpy().ctypes.data_as(ctypes.c_void_p), int(with_noise), ptr(noise), seed,
                                chain_base, ptr(eps_log), int(eps_log_steps), ptr(ws), nbytes, _lib.stream_ptr(dev)),
@@ -369,10 +383,14 @@ def reverse_sweep(Q, xemb, zt, noise=None, seed=None, chain_base=0, eps_log_step
 STREAM_GUIDE = 0x54  # DAMC_STREAM_GUIDE (csrc/common.h): the Philox stream of the guided sweep's prior-embedding noise
 
 
-def guided_sweep(Q, xemb, xemb_unc, zt, w, noise=None, seed=None, chain_base=0, eps_log_steps=0, with_noise=None):
+def guided_sweep(Q, xemb, xemb_unc, zt, w, noise=None, seed=None, chain_base=0, eps_log_steps=0, with_noise=None,
+                 draws=None):
     """In-place guided (classifier-free guidance, cond_w = w > 0) latent reverse sweep on zt (B, nz) in one
     damc_guided_sweep call; xemb (B, nxemb) the conditional embedding, xemb_unc (n, B, nxemb) the unconditional one of
-    every step in sweep order.  Returns the guided eps of the first eps_log_steps steps.  Mirrors reverse_sweep."""
+    every step in sweep order.  Returns the guided eps of the first eps_log_steps steps.  Mirrors reverse_sweep, but
+    for draws=: the guided sweep has no drawn variant."""
+    if draws is not None:
+        raise _lib.DamcError("guided_sweep(draws=...): the guided sweep has no device-resident draw state; use seed=")
     dev = zt.device
     plan = _DEN.get(Q.p)
     if plan is None:
@@ -409,7 +427,7 @@ def _guided_fits(Q, b, device):
     return int(_lib.lib().damc_guided_sweep_workspace_bytes(ctypes.byref(plan.pack(device)), b, int(Q.n_interval))) > 0
 
 
-def q_forward(Q, x=None, b=None, device=None, cond_w=-1, zt=None, seed=None, chain_base=0):
+def q_forward(Q, x=None, b=None, device=None, cond_w=-1, zt=None, seed=None, chain_base=0, draws=None):
     """_netQ_U.forward on the HIP path (diffusion_net.py:585-622).
 
     zt / seed / chain_base (not in the reference's signature; sharded callers only): the initial latent
@@ -420,8 +438,18 @@ def q_forward(Q, x=None, b=None, device=None, cond_w=-1, zt=None, seed=None, cha
     cond_w > 0 (classifier-free guidance, diffusion_net.py:595-620) runs the guided sweep, one launch sequence for
     all steps.  With a seed, the per-step prior-embedding noise is the library's Philox stream 0x54 keyed by the
     global chain index and the step noise the sweep's own in-kernel stream, so the same sharding rule holds; without
-    one, torch's draws are taken in the reference's order (_q_forward_guided)."""
+    one, torch's draws are taken in the reference's order (_q_forward_guided).
+
+    draws (a damc.graphs.DrawState, instead of seed): reverse_sweep's; a caller that captures the call passes zt too
+    (the default initial latent is a host-generator draw, which a graph would replay unchanged).  The guided sweep
+    raises DamcError."""
+    from .graphs import exclusive
+
+    exclusive(seed, draws, "q_forward")
     if cond_w is not None and cond_w > 0 and x is not None:
+        if draws is not None:
+            raise _lib.DamcError("q_forward(draws=...): the guided sweep (cond_w > 0) has no device-resident draw "
+                                 "state; use seed=")
         if Q.nz % 4:
             raise NotImplementedError("classifier-free guidance (cond_w > 0) is not implemented for nz % 4 != 0 "
                                       "(the toy amortizer): the guided sweep needs float4 rows")
@@ -446,7 +474,7 @@ def q_forward(Q, x=None, b=None, device=None, cond_w=-1, zt=None, seed=None, cha
         raise _lib.DamcError("the HIP sweep needs a ROCm device (got %s)" % zt.device)
     if zt.shape != (b, Q.nz):
         raise _lib.DamcError("zt must be (%d, %d)" % (b, Q.nz))
-    reverse_sweep(Q, xemb, zt, seed=seed, chain_base=chain_base)
+    reverse_sweep(Q, xemb, zt, seed=seed, chain_base=chain_base, draws=draws)
     return zt
 
 

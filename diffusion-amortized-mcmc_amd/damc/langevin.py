@@ -11,6 +11,12 @@ Spectral-norm nets in train mode (nn.utils.spectral_norm, diffusion_net.py:8-16)
 advances each layer's u, v by one power iteration, so the weights change from step to step.  The chains then run one
 step per library call, each after that step's power iterations (plans.spectral_norm_step) and a re-pack; the noise is
 the same Philox stream (keyed by step_offset + i), so a chain keeps its values whichever way it is cut.
+
+``draws=`` (a ``damc.graphs.DrawState``, instead of ``seed=``): the Philox key is read from device memory by the
+kernels, bitwise the seeded call with ``seed = state.seed`` and ``step_offset + state.counter``; a captured call then
+draws new noise on every replay.  posterior_langevin / prior_langevin advance the counter by ``n_steps`` after
+enqueueing; the per-op hooks (philox_normal, philox_uniform, z_update) do not.  Train-mode spectral-norm chains take
+one host-driven power iteration per step and refuse ``draws=``.
 """
 import ctypes
 
@@ -18,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .graphs import exclusive
 from .plans import ebm_plan, generator_plan, spectral_norm_step
 
 
@@ -35,11 +42,12 @@ def new_seed():
 
 
 def posterior_langevin(z, x, netG, netE, n_steps, sigma, step, with_noise, noise=None, seed=None,
-                       step_offset=0, chain_base=0, diag=False):
+                       step_offset=0, chain_base=0, diag=False, draws=None):
     """In-place n-step posterior Langevin (workspace/src/MCMC.py:48-74) on z (B, nz).
 
     Returns a (n_steps, 4) diagnostics tensor {sum E, lik, |z|^2/2, mean grad} if diag else None.
     """
+    exclusive(seed, draws, "posterior_langevin")
     _f32c(z, "z")
     dev = z.device
     x = x.to(device=dev, dtype=torch.float32).contiguous()
@@ -53,23 +61,29 @@ def posterior_langevin(z, x, netG, netE, n_steps, sigma, step, with_noise, noise
         noise = _f32c(noise.to(dev), "noise")
         if noise.numel() < n_steps * B * gp.nz:
             raise _lib.DamcError("noise must hold (n_steps, B, nz) values")
-    if seed is None:
+    if seed is None and draws is None:
         seed = new_seed() if (with_noise and noise is None) else 0
     dg = torch.zeros(max(n_steps, 1), 4, dtype=torch.float32, device=dev) if diag else None
+    L = _lib.lib()
+    fn, key = (L.damc_posterior_langevin, seed) if draws is None else (L.damc_posterior_langevin_ds, draws.ptr())
 
     def run(n, off, nz_, dg_):
         gdesc = gp.refresh(dev)
         edesc = ep.refresh(dev) if ep is not None else None
         ws, nbytes = gp.workspace(B)
-        check(_lib.lib().damc_posterior_langevin(
-            ctypes.byref(gdesc), ctypes.byref(edesc) if edesc is not None else None, ptr(z), ptr(x), B, int(n),
-            float(sigma), float(step), int(bool(with_noise)), ptr(nz_), seed, off, chain_base,
-            ptr(dg_), ptr(ws), nbytes, _lib.stream_ptr(dev)), "damc_posterior_langevin")
+        check(fn(ctypes.byref(gdesc), ctypes.byref(edesc) if edesc is not None else None, ptr(z), ptr(x), B, int(n),
+                 float(sigma), float(step), int(bool(with_noise)), ptr(nz_), key, off, chain_base,
+                 ptr(dg_), ptr(ws), nbytes, _lib.stream_ptr(dev)), "damc_posterior_langevin")
 
     sn = gp.sn_train() + (ep.sn_train() if ep is not None else [])
     if not sn:
         run(n_steps, step_offset, noise, dg)
+        if draws is not None:
+            draws.advance(n_steps)
         return dg
+    if draws is not None:
+        raise _lib.DamcError("posterior_langevin(draws=...): train-mode spectral-norm chains run one host-driven power "
+                             "iteration per step and cannot be replayed from a graph; use seed=")
     # train-mode spectral norm: netG(z) and netE(z) once per reference step (MCMC.py:54-58), one power iteration each
     nzs = noise.view(-1, B * gp.nz) if noise is not None else None
     for i in range(int(n_steps)):
@@ -118,7 +132,7 @@ def mfma_min_chains():
 
 
 def prior_langevin(z, netE, n_steps, step, with_noise, noise=None, seed=None, step_offset=0, chain_base=0,
-                   diag=False, engine="auto", global_batch=None):
+                   diag=False, engine="auto", global_batch=None, draws=None):
     """In-place n-step prior Langevin (workspace/src/MCMC.py:27-46), one persistent launch.
 
     engine: "auto" (by chain count), "valu" (one chain per workgroup, weights in registers) or "mfma" (16-chain
@@ -127,6 +141,7 @@ def prior_langevin(z, netE, n_steps, step, with_noise, noise=None, seed=None, st
     engine the unsharded block runs, and the union of the shards stays bitwise the one-GPU result.  Returns a
     (n_steps, 2) diagnostics tensor {sum E, |z|^2/2} if diag else None.
     """
+    exclusive(seed, draws, "prior_langevin")
     _f32c(z, "z")
     dev = z.device
     ep = ebm_plan(netE)
@@ -137,9 +152,11 @@ def prior_langevin(z, netE, n_steps, step, with_noise, noise=None, seed=None, st
         noise = _f32c(noise.to(dev), "noise")
         if noise.numel() < n_steps * B * ep.nz:
             raise _lib.DamcError("noise must hold (n_steps, B, nz) values")
-    if seed is None:
+    if seed is None and draws is None:
         seed = new_seed() if (with_noise and noise is None) else 0
     dg = torch.zeros(max(n_steps, 1), 2, dtype=torch.float32, device=dev) if diag else None
+    L = _lib.lib()
+    fn, key = (L.damc_prior_langevin_engine, seed) if draws is None else (L.damc_prior_langevin_ds, draws.ptr())
     if engine not in PRIOR_ENGINES:
         raise ValueError("engine must be one of %s" % sorted(PRIOR_ENGINES))
     code = PRIOR_ENGINES[engine]
@@ -150,9 +167,8 @@ def prior_langevin(z, netE, n_steps, step, with_noise, noise=None, seed=None, st
         edesc = ep.refresh(dev)
 
         def call(c):
-            return _lib.lib().damc_prior_langevin_engine(ctypes.byref(edesc), ptr(z), B, int(n), float(step),
-                                                         int(bool(with_noise)), ptr(nz_), seed, off,
-                                                         chain_base, ptr(dg_), c, _lib.stream_ptr(dev))
+            return fn(ctypes.byref(edesc), ptr(z), B, int(n), float(step), int(bool(with_noise)), ptr(nz_), key, off,
+                      chain_base, ptr(dg_), c, _lib.stream_ptr(dev))
 
         rc = call(code)
         if rc == _lib.DAMC_ERR_UNSUPPORTED and engine == "auto":  # the shape has no kernel of that engine: the other
@@ -162,7 +178,12 @@ def prior_langevin(z, netE, n_steps, step, with_noise, noise=None, seed=None, st
     sn = ep.sn_train()
     if not sn:
         run(n_steps, step_offset, noise, dg)
+        if draws is not None:
+            draws.advance(n_steps)
         return dg
+    if draws is not None:
+        raise _lib.DamcError("prior_langevin(draws=...): train-mode spectral-norm chains run one host-driven power "
+                             "iteration per step and cannot be replayed from a graph; use seed=")
     # train-mode spectral norm: netE(z) once per reference step (MCMC.py:32), one power iteration each
     nzs = noise.view(-1, B * ep.nz) if noise is not None else None
     for i in range(int(n_steps)):
@@ -184,24 +205,40 @@ def ebm_energy_grad(z, netE):
     return e, g
 
 
-def philox_normal(n_steps, batch, nz, seed, device, step_offset=0, chain_base=0, stream_id=0x51):
+def philox_normal(n_steps, batch, nz, seed=None, device=None, step_offset=0, chain_base=0, stream_id=0x51, draws=None):
+    exclusive(seed, draws, "philox_normal")
+    if seed is None and draws is None:
+        raise _lib.DamcError("philox_normal: needs seed= or draws=")
     out = torch.empty(n_steps, batch, nz, dtype=torch.float32, device=device)
+    if draws is not None:
+        check(_lib.lib().damc_philox_normal_ds(ptr(out), n_steps, batch, nz, draws.ptr(), step_offset, chain_base,
+                                               stream_id, _lib.stream_ptr(device)), "damc_philox_normal_ds")
+        return out
     check(_lib.lib().damc_philox_normal(ptr(out), n_steps, batch, nz, seed, step_offset, chain_base, stream_id,
                                         _lib.stream_ptr(device)), "damc_philox_normal")
     return out
 
 
-def philox_uniform(n_steps, batch, seed, device, step_offset=0, chain_base=0, stream_id=_lib.STREAM_QU):
+def philox_uniform(n_steps, batch, seed=None, device=None, step_offset=0, chain_base=0, stream_id=_lib.STREAM_QU,
+                   draws=None):
     """(n_steps, batch) U[0, 1) values on the 2^-24 grid (torch.rand's interval), keyed like philox_normal: row r of
     step i is word 0 of the block of (seed, chain_base + r, step_offset + i, quad 0, stream_id)."""
+    exclusive(seed, draws, "philox_uniform")
+    if seed is None and draws is None:
+        raise _lib.DamcError("philox_uniform: needs seed= or draws=")
     out = torch.empty(n_steps, batch, dtype=torch.float32, device=device)
+    if draws is not None:
+        check(_lib.lib().damc_philox_uniform_ds(ptr(out), n_steps, batch, draws.ptr(), step_offset, chain_base,
+                                                stream_id, _lib.stream_ptr(device)), "damc_philox_uniform_ds")
+        return out
     check(_lib.lib().damc_philox_uniform(ptr(out), n_steps, batch, seed, step_offset, chain_base, stream_id,
                                          _lib.stream_ptr(device)), "damc_philox_uniform")
     return out
 
 
-def z_update(z, g, step, with_noise, noise=None, seed=0, step_index=0, chain_base=0):
+def z_update(z, g, step, with_noise, noise=None, seed=None, step_index=0, chain_base=0, draws=None):
     """Per-op hook: z <- z - 0.5 step^2 (g + z) (+ step xi), in place (MCMC.py:36-38,62-64)."""
+    exclusive(seed, draws, "z_update")
     _f32c(z, "z")
     _f32c(g, "g")
     if g.shape != z.shape:
@@ -210,7 +247,12 @@ def z_update(z, g, step, with_noise, noise=None, seed=0, step_index=0, chain_bas
         noise = _f32c(noise, "noise")
         if noise.numel() < z.numel():
             raise _lib.DamcError("noise must hold (B, nz) values")
+    if draws is not None:
+        check(_lib.lib().damc_z_update_ds(ptr(z), ptr(g), z.shape[0], z.shape[1], float(step), int(bool(with_noise)),
+                                          ptr(noise), draws.ptr(), step_index, chain_base,
+                                          _lib.stream_ptr(z.device)), "damc_z_update_ds")
+        return z
     check(_lib.lib().damc_z_update(ptr(z), ptr(g), z.shape[0], z.shape[1], float(step), int(bool(with_noise)),
-                                   ptr(noise), seed, step_index, chain_base, _lib.stream_ptr(z.device)),
+                                   ptr(noise), seed or 0, step_index, chain_base, _lib.stream_ptr(z.device)),
           "damc_z_update")
     return z

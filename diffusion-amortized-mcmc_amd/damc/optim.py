@@ -14,7 +14,19 @@ alone and is built once.  ``clip_grad_norm_`` is the deterministic HIP norm plus
 the total norm like torch's.  ``clip_and_step(max_norm)`` fuses the two: the norm pass, then the Adam pass
 applies the clip factor (and leaves the gradients scaled, as ``clip_grad_norm_`` would have).  There is no
 fallback: CPU tensors, non-fp32 or non-contiguous tensors, and the unsupported flags (amsgrad, maximize,
-capturable, differentiable, tensor lr) raise.
+differentiable, tensor betas; a tensor lr without capturable) raise.
+
+``capturable=True`` (torch's flag and state format): ``step`` is a 0-d fp32 tensor on the parameters' device, shared
+by the parameters of a group that step together, advanced on the device and read by ``damc_adam_step_capturable``,
+which evaluates the bias corrections in the kernel (in double, as the host path's Python floats).  ``step()`` and
+``clip_and_step()`` then neither synchronise nor allocate outside torch's allocator, so a ``torch.cuda.CUDAGraph``
+can record them and every replay takes the next step.  ``lr`` may be a 0-d fp32 device tensor, read by the kernel on
+every launch; a float ``lr`` is a kernel argument and therefore FIXED AT CAPTURE: a loop that changes
+``param_groups[i]["lr"]`` between replays (the reference driver decays it every 1000 iterations) needs a tensor
+``lr`` (``lr_tensor.fill_(new)`` or ``copy_``) or a re-capture.  Results agree with the non-capturable form to the
+last place of the device's and the host's ``pow``.  ``state_dict()`` / ``load_state_dict()`` interchange with
+``torch.optim.Adam/AdamW(capturable=True)`` and with the non-capturable forms: on load ``step`` moves to the
+parameter's device (capturable) or to the CPU (not), and the optimiser keeps its own ``capturable`` flag.
 """
 import ctypes
 
@@ -103,11 +115,18 @@ class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *,
                  foreach=None, maximize=False, capturable=False, differentiable=False, fused=None,
                  decoupled_weight_decay=False):
-        if amsgrad or maximize or capturable or differentiable:
-            raise NotImplementedError("damc.optim.Adam: amsgrad / maximize / capturable / differentiable")
-        if isinstance(lr, torch.Tensor) or any(isinstance(b, torch.Tensor) for b in betas):
-            raise NotImplementedError("damc.optim.Adam: tensor lr / betas")
-        if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+        if amsgrad or maximize or differentiable:
+            raise NotImplementedError("damc.optim.Adam: amsgrad / maximize / differentiable")
+        if any(isinstance(b, torch.Tensor) for b in betas):
+            raise NotImplementedError("damc.optim.Adam: tensor betas")
+        if isinstance(lr, torch.Tensor):
+            if not capturable:
+                raise NotImplementedError("damc.optim.Adam: a tensor lr needs capturable=True")
+            if lr.numel() != 1:
+                raise ValueError("Tensor lr must be 1-element")
+        elif not 0.0 <= lr:
+            raise ValueError("invalid Adam hyper-parameters")
+        if not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError("invalid Adam hyper-parameters")
         if not 0.0 <= weight_decay:
             raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
@@ -132,6 +151,31 @@ class Adam(torch.optim.Optimizer):
                        for k, v in sd["state"].items()}
         return sd
 
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict, between the capturable and the non-capturable form in either
+        direction (torch's own or this module's): every group keeps THIS optimiser's ``capturable`` flag, and ``step``
+        lands where that form reads it -- a 0-d fp32 tensor on the parameter's device, one tensor shared by the
+        parameters of a group whose counts agree (one launch per 96 of them), or a CPU scalar.  Eager only: the counts
+        are read on the host."""
+        flags = [g["capturable"] for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, cap in zip(self.param_groups, flags):
+            group["capturable"] = cap
+            shared = {}
+            for p in group["params"]:
+                st = self.state.get(p)
+                if not st or "step" not in st:
+                    continue
+                t = st["step"]
+                if not cap:
+                    st["step"] = (t.detach().to(device="cpu", dtype=torch.float32) if isinstance(t, torch.Tensor)
+                                  else torch.tensor(float(t), dtype=torch.float32))
+                    continue
+                key = (float(t), p.device)
+                if key not in shared:
+                    shared[key] = torch.tensor(key[0], dtype=torch.float32, device=p.device)
+                st["step"] = shared[key]
+
     def zero_grad(self, set_to_none=True):
         """torch.optim.Optimizer.zero_grad; set_to_none (the default) as a plain loop (torch's walks the same
         parameters through its profiler scope and foreach grouping: ~0.1 ms of host time per Q update)."""
@@ -145,6 +189,7 @@ class Adam(torch.optim.Optimizer):
         """(params, grads, exp_avgs, exp_avg_sqs, steps) of the group's parameters that have a gradient."""
         ps, gs, ms, vs, steps = [], [], [], [], []
         f32, strided = torch.float32, torch.strided
+        capturable, fresh = group["capturable"], {}
         for p in group["params"]:
             g = p.grad
             if g is None:
@@ -157,7 +202,12 @@ class Adam(torch.optim.Optimizer):
                 _require_fp32_cuda(g, "grad")
             st = self.state[p]
             if len(st) == 0:
-                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                if capturable:  # torch's capturable state: a device scalar; the parameters that start together share it
+                    if p.device not in fresh:
+                        fresh[p.device] = torch.zeros((), dtype=torch.float32, device=p.device)
+                    st["step"] = fresh[p.device]
+                else:
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             ps.append(p)
@@ -232,10 +282,64 @@ class Adam(torch.optim.Optimizer):
             _check(L.damc_adam_step(_VP(dev.data_ptr()), n, _ptrs(ps[t0:t1]), _ptrs(gs[t0:t1]), _ptrs(ms[t0:t1]),
                                     _ptrs(vs[t0:t1]), t1 - t0, ctypes.byref(h), cp, s), "damc_adam_step")
 
+    def _hold(self, chunks):
+        """A capturable optimiser keeps its chunk tables alive itself: a recorded graph reads their device memory on
+        every replay, whatever the shared cache (_Chunks.of) evicts in the meantime."""
+        self.__dict__.setdefault("_held_chunks", {})[id(chunks)] = chunks
+        return chunks
+
+    def _run_capturable(self, group, ps, gs, ms, vs, steps, clip):
+        """One step with the counts on the device: nothing here reads them.  The parameters are grouped by the IDENTITY
+        of their step tensor (one per group in the steady state: _collect and load_state_dict share it); each tensor is
+        advanced once, on the device, by the first launch that reads it.  A tensor also held by a parameter that sits
+        this step out (no gradient) is cloned for the ones that step, so the idle parameter keeps its count."""
+        L = _lib.lib()
+        lr = group["lr"]
+        hp = _lib.AdamCapturable()
+        hp.beta1, hp.beta2 = group["betas"]
+        hp.eps, hp.weight_decay = group["eps"], group["weight_decay"]
+        hp.decoupled = 1 if group["decoupled_weight_decay"] else 0
+        lr_ptr = None
+        if isinstance(lr, torch.Tensor):
+            if not lr.is_cuda or lr.dtype != torch.float32 or lr.device != ps[0].device:
+                raise _lib.DamcError("capturable lr tensor: needs a float32 scalar on the parameters' device")
+            lr_ptr = _VP(lr.data_ptr())
+        else:
+            hp.lr = lr
+        idle = set()
+        if len(ps) < len(group["params"]):
+            idle = {id(self.state[p]["step"]) for p in group["params"]
+                    if p.grad is None and "step" in (self.state.get(p) or {})}
+        buckets = {}
+        for i, t in enumerate(steps):
+            buckets.setdefault(id(t), []).append(i)
+        clip_ptr = _VP(clip.data_ptr()) if clip is not None else None
+        s = _stream()
+        for key, idx in buckets.items():
+            step = steps[idx[0]]
+            if step.device != ps[idx[0]].device or step.dtype != torch.float32:
+                raise _lib.DamcError("capturable step state must be a float32 scalar on the parameter's device")
+            if key in idle:
+                step = step.clone()
+                for i in idx:
+                    self.state[ps[i]]["step"] = step
+            whole = len(idx) == len(ps)
+            bp, bg, bm, bv = ((ps, gs, ms, vs) if whole else
+                              tuple([seq[i] for i in idx] for seq in (ps, gs, ms, vs)))
+            chunks = self._hold(_Chunks.of([p.numel() for p in bp], bp[0].device))
+            for k, (t0, t1, dev, n, _) in enumerate(chunks.slices):
+                _check(L.damc_adam_step_capturable(_VP(dev.data_ptr()), n, _ptrs(bp[t0:t1]), _ptrs(bg[t0:t1]),
+                                                   _ptrs(bm[t0:t1]), _ptrs(bv[t0:t1]), t1 - t0, ctypes.byref(hp),
+                                                   _VP(step.data_ptr()), 1 if k == 0 else 0, lr_ptr, clip_ptr, s),
+                       "damc_adam_step_capturable")
+
     def _run(self, clip=None, collected=None):
         for gi, group in enumerate(self.param_groups):
             ps, gs, ms, vs, steps = collected[gi] if collected is not None else self._collect(group)
             if not ps:
+                continue
+            if group["capturable"]:
+                self._run_capturable(group, ps, gs, ms, vs, steps, clip)
                 continue
             common = self._advance_steps(group, steps)
             if common is not None:
@@ -265,7 +369,10 @@ class Adam(torch.optim.Optimizer):
         grads = [g for c in collected for g in c[1]]
         if not grads:
             return torch.tensor(0.0)
-        out = _norm(_Chunks.of([g.numel() for g in grads], grads[0].device), grads, max_norm)
+        chunks = _Chunks.of([g.numel() for g in grads], grads[0].device)
+        if any(g["capturable"] for g in self.param_groups):
+            self._hold(chunks)
+        out = _norm(chunks, grads, max_norm)
         self._run(clip=out, collected=collected)
         self.last_grad_norm = out[0]
         return out[0]

@@ -455,11 +455,18 @@ def q_noise_glue(q, u, z, eps, logsnr_out=None):
     return zt, se
 
 
-def q_noise_glue_seeded(q, z, seed, draw_index=0, chain_base=0, u_out=None, logsnr_out=None):
+def q_noise_glue_seeded(q, z, seed=None, draw_index=0, chain_base=0, u_out=None, logsnr_out=None, draws=None):
     """(zt, temb_in, eps) of the seeded Q.calculate_loss in one launch (damc_q_noise_glue_seeded): q_noise_glue with u
     and eps drawn in the kernel from the Philox streams STREAM_QU / STREAM_QEPS, keyed (seed, chain_base + row,
     draw_index) -- a row's noise depends on its global index and the update's index, not on the rank that holds it.
-    u_out (B) / logsnr_out (B) receive the draws' u and the schedule's logsnr (tests)."""
+    u_out (B) / logsnr_out (B) receive the draws' u and the schedule's logsnr (tests).
+    draws (a damc.graphs.DrawState, instead of seed): the key is read on the device (damc_q_noise_glue_seeded_ds),
+    bitwise the seeded call with the state's seed and draw_index + its counter; the counter is not advanced here."""
+    from .graphs import exclusive
+
+    exclusive(seed, draws, "q_noise_glue_seeded")
+    if seed is None and draws is None:
+        raise _lib.DamcError("q_noise_glue_seeded: needs seed= or draws=")
     if z.device.type != "cuda" or z.dtype != torch.float32 or z.dim() != 2:
         raise _lib.DamcError("q_noise_glue_seeded: z must be a (B, nz) float32 tensor on a ROCm device (got %s %s); the "
                              "seeded draws have no CPU fallback" % (z.dtype, z.device))
@@ -470,6 +477,12 @@ def q_noise_glue_seeded(q, z, seed, draw_index=0, chain_base=0, u_out=None, logs
     zt = torch.empty(B, nz, dtype=torch.float32, device=dev)
     se = torch.empty(B, ntemb, dtype=torch.float32, device=dev)
     eps = torch.empty(B, nz, dtype=torch.float32, device=dev)
+    if draws is not None:
+        check(_lib.lib().damc_q_noise_glue_seeded_ds(ptr(z), B, nz, float(q.logsnr_min), float(q.logsnr_max),
+                                                     ptr(_freqs(ntemb // 2, dev)), ntemb, draws.ptr(), int(draw_index),
+                                                     int(chain_base), ptr(u_out), ptr(eps), ptr(logsnr_out), ptr(zt),
+                                                     ptr(se), _lib.stream_ptr(dev)), "damc_q_noise_glue_seeded_ds")
+        return zt, se, eps
     check(_lib.lib().damc_q_noise_glue_seeded(ptr(z), B, nz, float(q.logsnr_min), float(q.logsnr_max),
                                               ptr(_freqs(ntemb // 2, dev)), ntemb, int(seed), int(draw_index),
                                               int(chain_base), ptr(u_out), ptr(eps), ptr(logsnr_out), ptr(zt), ptr(se),

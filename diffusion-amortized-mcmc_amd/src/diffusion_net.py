@@ -317,7 +317,7 @@ class _QBase(nn.Module):
         """xemb of calculate_loss: the encoder under autograd (_EncoderBase.forward picks libdamc's training path)."""
         return self.encoder(x)
 
-    def calculate_loss(self, x=None, z=None, mask=None, seed=None, draw_index=0, chain_base=0):
+    def calculate_loss(self, x=None, z=None, mask=None, seed=None, draw_index=0, chain_base=0, draws=None):
         """Training loss of the denoiser (diffusion_net.py:624-645; the toy's is the same lines,
         toy_example/src/diffusion_net.py:241-263).  On ROCm tensors the denoiser's forward and
         backward run on libdamc (Diffusion_UnetA.forward -> damc.training.denoiser_apply), as do the encoder's
@@ -332,8 +332,18 @@ class _QBase(nn.Module):
         draw_index) instead of torch's generator -- prior_emb's noise from damc.langevin.philox_normal (STREAM_QPE), u
         and eps inside the noising launch (damc.training.q_noise_glue_seeded) -- so a row's noise depends on its global
         index and the update's index only, whichever rank holds it; no torch generator is consulted.  The seeded draws
-        exist on the libdamc path alone: anything else raises DamcError."""
+        exist on the libdamc path alone: anything else raises DamcError.
+
+        draws (a damc.graphs.DrawState, instead of seed; graph-replayed training): the same three draws with the key
+        read on the device -- bitwise calculate_loss(seed=state.seed, draw_index=draw_index + state.counter) -- and the
+        counter advanced by 1 once all three have been enqueued, so a captured update draws the next index on its next
+        replay.  The unseeded loss (torch's generator) has no such form."""
         assert z is not None
+        if draws is not None:
+            from damc.graphs import exclusive
+
+            exclusive(seed, draws, "calculate_loss")
+            return self._calculate_loss_seeded(x, z, mask, None, draw_index, chain_base, draws)
         if seed is not None:
             return self._calculate_loss_seeded(x, z, mask, seed, draw_index, chain_base)
         if x is not None:
@@ -365,7 +375,7 @@ class _QBase(nn.Module):
         return 0.5 * torch.sum((eps - eps_pred) ** 2, dim=1)
 
 
-    def _calculate_loss_seeded(self, x, z, mask, seed, draw_index, chain_base):
+    def _calculate_loss_seeded(self, x, z, mask, seed, draw_index, chain_base, draws=None):
         from damc import _lib, langevin, training
 
         if not (z.is_cuda and z.dtype == torch.float32 and not z.requires_grad and (x is None or x.is_cuda)):
@@ -378,7 +388,7 @@ class _QBase(nn.Module):
 
         def prior_noise(n):
             return langevin.philox_normal(1, n, self.nz, seed, z.device, step_offset=draw_index, chain_base=chain_base,
-                                          stream_id=_lib.STREAM_QPE)[0]
+                                          stream_id=_lib.STREAM_QPE, draws=draws)[0]
 
         if x is not None:
             xemb = self._encode_for_loss(x)
@@ -386,7 +396,9 @@ class _QBase(nn.Module):
                 xemb = xemb * mask + self._prior_emb(prior_noise(len(x))) * (1 - mask)
         else:
             xemb = self._prior_emb(prior_noise(len(z)))
-        zt, se, eps = training.q_noise_glue_seeded(self, z, seed, draw_index, chain_base)
+        zt, se, eps = training.q_noise_glue_seeded(self, z, seed, draw_index, chain_base, draws=draws)
+        if draws is not None:  # every draw of this update has been enqueued at the same index
+            draws.advance(1)
         return training.q_loss(eps, training.denoiser_apply(self.p, zt, se, xemb))
 
 

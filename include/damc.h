@@ -90,6 +90,24 @@ typedef struct {
   const float *w1t, *w2t;                     /* packed transposes (damc_pack_ebm)                  */
 } damc_ebm_t;
 
+/* Draw state: a Philox key in DEVICE memory (16 bytes, 8-B aligned), for callers that capture the seeded entry points
+ * in a HIP graph.  A host seed and offset are kernel arguments, fixed at capture, so a replay would draw the same
+ * noise again; the drawn variants (suffix _ds) below take `const damc_draw_state_t* state` where the entry point of
+ * the same name takes `seed`, and their kernels read the two words from device memory at run time:
+ *   result == the seeded entry point called with seed = state->seed and
+ *             step_offset (step_index, draw_index; 0 for the sweep) = the host value + state->counter, bit for bit.
+ * They launch the kernels the seeded entry points launch (which pass a null state) and nothing else: no extra launch,
+ * no host read, no synchronisation; the state is read once per launch or workgroup (team sweep and launch chain: by
+ * the setup kernel that writes the sweep's device-resident call record).  A drawn variant never advances the state:
+ * the caller enqueues damc_draw_state_advance after the calls that share a counter value.  state == NULL returns
+ * DAMC_ERR_ARG before any launch.  The guided sweep has no drawn variant. */
+typedef struct {
+  uint64_t seed;
+  uint64_t counter;
+} damc_draw_state_t;
+/* counter += delta, by a one-thread kernel on `stream` (stream-ordered and capturable like every other call) */
+int damc_draw_state_advance(damc_draw_state_t* state, uint64_t delta, void* stream);
+
 /* ---------------------------------------------------------------- library / packing */
 int damc_abi_version(void);
 const char* damc_error_string(int code);
@@ -115,6 +133,12 @@ int damc_posterior_langevin(const damc_generator_t* g, const damc_ebm_t* ebm, fl
                             int batch, int n_steps, double sigma, double step, int with_noise,
                             const float* noise, uint64_t seed, uint64_t step_offset, uint64_t chain_base,
                             float* diag, void* workspace, size_t workspace_bytes, void* stream);
+
+/* the drawn variant (damc_draw_state_t above): step i draws at step_offset + state->counter + i */
+int damc_posterior_langevin_ds(const damc_generator_t* g, const damc_ebm_t* ebm, float* z, const float* x, int batch,
+                               int n_steps, double sigma, double step, int with_noise, const float* noise,
+                               const damc_draw_state_t* state, uint64_t step_offset, uint64_t chain_base, float* diag,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* per-op hooks (parity tests): grad_z |G(z)-x|^2/(2 sigma^2) -> grad (B,nz) */
 int damc_likelihood_grad(const damc_generator_t* g, const float* z, const float* x, int batch, double sigma,
@@ -175,6 +199,10 @@ int damc_ebm_mfma_min_chains(void);
 int damc_prior_langevin_engine(const damc_ebm_t* ebm, float* z, int batch, int n_steps, double step, int with_noise,
                                const float* noise, uint64_t seed, uint64_t step_offset, uint64_t chain_base,
                                float* diag, int engine, void* stream);
+/* the drawn variant of damc_prior_langevin_engine (damc_draw_state_t above) */
+int damc_prior_langevin_ds(const damc_ebm_t* ebm, float* z, int batch, int n_steps, double step, int with_noise,
+                           const float* noise, const damc_draw_state_t* state, uint64_t step_offset,
+                           uint64_t chain_base, float* diag, int engine, void* stream);
 /* per-op hook: energy (B) and grad_z sum E (B,nz) */
 int damc_ebm_energy_grad(const damc_ebm_t* ebm, const float* z, int batch, float* energy, float* grad,
                          void* stream);
@@ -183,6 +211,8 @@ int damc_ebm_grad(const damc_ebm_t* ebm, const float* z, int batch, float* energ
 /* per-op hook: z <- z - 0.5 step^2 (g + z) (+ step xi) ; g (B,nz) */
 int damc_z_update(float* z, const float* g, int batch, int nz, double step, int with_noise, const float* noise,
                   uint64_t seed, uint64_t step_index, uint64_t chain_base, void* stream);
+int damc_z_update_ds(float* z, const float* g, int batch, int nz, double step, int with_noise, const float* noise,
+                     const damc_draw_state_t* state, uint64_t step_index, uint64_t chain_base, void* stream);
 /* Philox N(0,1) draw used by every Langevin kernel (statistical tests) -> out (n_steps,B,nz) */
 int damc_philox_normal(float* out, int n_steps, int batch, int nz, uint64_t seed, uint64_t step_offset,
                        uint64_t chain_base, uint32_t stream_id, void* stream);
@@ -191,6 +221,11 @@ int damc_philox_normal(float* out, int n_steps, int batch, int nz, uint64_t seed
  * half-open interval on the 2^-24 grid (the normals keep their (0, 1] uniforms). */
 int damc_philox_uniform(float* out, int n_steps, int batch, uint64_t seed, uint64_t step_offset, uint64_t chain_base,
                         uint32_t stream_id, void* stream);
+/* the drawn variants of the two (damc_draw_state_t above) */
+int damc_philox_normal_ds(float* out, int n_steps, int batch, int nz, const damc_draw_state_t* state,
+                          uint64_t step_offset, uint64_t chain_base, uint32_t stream_id, void* stream);
+int damc_philox_uniform_ds(float* out, int n_steps, int batch, const damc_draw_state_t* state, uint64_t step_offset,
+                           uint64_t chain_base, uint32_t stream_id, void* stream);
 
 /* ------------------------------------------------- per-sample posterior energy (anomaly score) */
 /* The anomaly drivers' score (workspace/eval_anomaly_det.py:114-117, train_anomaly_det.py:223-226) per sample, with
@@ -446,6 +481,12 @@ int damc_reverse_sweep(const damc_denoiser_t* d, const float* xemb, float* zt, i
                        const float* temb_in, const float* coef, int with_noise, const float* noise, uint64_t seed,
                        uint64_t chain_base, float* eps_log, int eps_log_steps, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* the drawn variant (damc_draw_state_t above): noisy step k draws at state->counter + k, in every form of the sweep
+ * (team launch, launch chain, row-resident) */
+int damc_reverse_sweep_ds(const damc_denoiser_t* d, const float* xemb, float* zt, int batch, int n_steps,
+                          const float* temb_in, const float* coef, int with_noise, const float* noise,
+                          const damc_draw_state_t* state, uint64_t chain_base, float* eps_log, int eps_log_steps,
+                          void* workspace, size_t workspace_bytes, void* stream);
 /* the same under SURVEY.md §8b's name */
 int damc_q_reverse_sweep(const damc_denoiser_t* d, const float* xemb, float* zt, int batch, int n_steps,
                          const float* temb_in, const float* coef, int with_noise, const float* noise, uint64_t seed,
@@ -544,6 +585,11 @@ int damc_q_noise_glue(const float* u, const float* z, const float* eps, int batc
 int damc_q_noise_glue_seeded(const float* z, int batch, int nz, float logsnr_min, float logsnr_max, const float* freqs,
                              int ntemb, uint64_t seed, uint64_t draw_index, uint64_t chain_base, float* u, float* eps,
                              float* logsnr, float* zt, float* temb_in, void* stream);
+/* the drawn variant (damc_draw_state_t above): the update's index is draw_index + state->counter */
+int damc_q_noise_glue_seeded_ds(const float* z, int batch, int nz, float logsnr_min, float logsnr_max,
+                                const float* freqs, int ntemb, const damc_draw_state_t* state, uint64_t draw_index,
+                                uint64_t chain_base, float* u, float* eps, float* logsnr, float* zt, float* temb_in,
+                                void* stream);
 /* loss (B) = 0.5 * sum_j (eps - eps_pred)^2 (diffusion_net.py:642), and grad_eps_pred (B, nz) from grad_loss (B, element
  * stride grad_stride: 0 for the broadcast gradient of a .mean()) */
 int damc_q_loss_forward(const float* eps, const float* eps_pred, int batch, int nz, float* loss, void* stream);
@@ -672,6 +718,22 @@ int damc_grad_pack(const void* dev_chunks, int nchunks, const float* const* grad
 int damc_adam_step(const void* dev_chunks, int nchunks, float* const* params, float* const* grads,
                    float* const* exp_avgs, float* const* exp_avg_sqs, int ntensors, const damc_adam_hparams_t* hp,
                    const float* clip, void* stream);
+
+/* The same step for a caller that captures it in a HIP graph (torch.optim's capturable=True): the step count is a
+ * DEVICE fp32 scalar, so nothing the host computes from it is baked into the launch.  advance != 0 first adds 1 to
+ * *step (a one-thread kernel on the stream; pass 0 for the second and later <= 96-tensor slices of one step); the
+ * step kernel then reads *step and evaluates 1 - beta1^t, sqrt(1 - beta2^t), lr / (1 - beta1^t) and 1 - lr wd in
+ * double, rounds each to fp32 once -- what the caller of damc_adam_step does on the host -- and runs
+ * damc_adam_step's element arithmetic.  lr: a device fp32 scalar read by the kernel, or NULL for hp->lr (then fixed
+ * at capture).  Against damc_adam_step the results agree to the last place of the device's and the host's pow. */
+typedef struct {
+  double lr, beta1, beta2, eps, weight_decay;
+  int decoupled; /* AdamW */
+} damc_adam_capturable_t;
+int damc_adam_step_capturable(const void* dev_chunks, int nchunks, float* const* params, float* const* grads,
+                              float* const* exp_avgs, float* const* exp_avg_sqs, int ntensors,
+                              const damc_adam_capturable_t* hp, float* step, int advance, const float* lr,
+                              const float* clip, void* stream);
 
 /* ------------------------------------------------------------ FID statistics */
 /* calculate_fid* (workspace/src/MCMC.py:130-176) reduce Inception pool features to (mu, sigma) before the
