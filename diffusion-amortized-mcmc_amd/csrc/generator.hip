@@ -146,6 +146,12 @@ __global__ __launch_bounds__(256) void slab_sum4_kernel(const float* __restrict_
   }
 }
 
+// p[0 .. n) = 0: the slab slices a shortened split-K never writes (dz_slabs)
+__global__ __launch_bounds__(256) void zero_floats_kernel(float* __restrict__ p, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = 0.f;
+}
+
 int slab_sum(const float* slabs, int nslab, long n, float* out, hipStream_t s) {
   ProfScope ps("slab_sum", 0.0, s);
   if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(slabs) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
@@ -678,8 +684,16 @@ int dz_slabs(const damc_generator_t* g, int B, Workspace& ws, const float* d, hi
   a.K = (int)K;
   a.k_per_z = proj_k_per(K, ws.nslab);
   const int S = (int)((K + a.k_per_z - 1) / a.k_per_z);
-  // slices beyond S (when rounding shrank the count) must contribute zeros
-  if (S < ws.nslab) DAMC_CHECK(hipMemsetAsync(ws.slabs, 0, sizeof(float) * ws.nslab * (size_t)B * L0.cin, s));
+  // slices beyond S (when rounding shrank the count) must contribute zeros.  Written by a kernel: this used to be a
+  // hipMemsetAsync of all the slabs, the one kind of node a replayed graph does not order before the kernels behind
+  // it; a captured G update then replayed with the memset landing on slices the GEMM had already
+  // written (tests/test_gpu_gen_ops.py, the 7 x 7 first layer: 11 of 12 slices run)
+  if (S < ws.nslab) {
+    const long n = (long)(ws.nslab - S) * B * L0.cin;
+    hipLaunchKernelGGL(zero_floats_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       ws.slabs + (long)S * B * L0.cin, n);
+    DAMC_LAUNCH_CHECK();
+  }
   return damc::launch_gemm(a, km ? damc::A_CONV : damc::A_DENSE, damc::EPI_STORE, damc::O_DENSE, S, "proj_dgrad",
                            2.0 * B * (double)K * L0.cin, s);
 }
@@ -725,6 +739,28 @@ void up2_wgrad_split(const damc_layer_t& L, int Bp, int* S, int* kper) {
   const long kp = (nkt + sl - 1) / sl * 32;
   *kper = (int)kp;
   *S = (int)((K + kp - 1) / kp);
+}
+
+// What train_backward's launches refuse by shape, asked on the host before the first launch of the G update (a
+// refusal half way through the backward would come after out_delta and the output layer's kernels had run and the
+// train record was consumed): launch_wgrad_x3 takes N = Cout (k4 s2 p1) or Cout k0 k0 (first layer) in whole octets
+// and operands within 32-bit byte offsets; launch_smallc_wgrad has an instantiation and an LDS window for the output
+// layer.  The plain forward and the Langevin entry points do not depend on any of this.
+int train_supported(const damc_generator_t* g, int B) {
+  const int Bp = bp_of(B);
+  for (int i = 0; i < g->n_layers; ++i) {
+    const damc_layer_t& L = g->layers[i];
+    if (L.kind == DAMC_LAYER_UP2 || L.kind == DAMC_LAYER_PROJ) {
+      const bool up2 = L.kind == DAMC_LAYER_UP2;
+      const long N = up2 ? L.cout : (long)L.cout * L.hout * L.wout;
+      const double K = (double)(up2 ? (long)L.hin * L.win : 1L) * Bp;
+      if (N % 8 != 0) return DAMC_ERR_UNSUPPORTED;
+      if (K >= 2147483647.0 || L.cin * K * 6 >= 2147483647.0 || N * K * 6 >= 2147483647.0) return DAMC_ERR_UNSUPPORTED;
+    } else if (L.kind == DAMC_LAYER_SMALLC) {
+      if (int rc = damc::smallc_wgrad_supported(L, B)) return rc;
+    }
+  }
+  return 0;
 }
 
 size_t carve_train(const damc_generator_t* g, int B, char* base, TrainWs* t) {
@@ -1177,7 +1213,7 @@ extern "C" int damc_posterior_langevin_ds(const damc_generator_t* g, const damc_
 
 // ------------------------------------------------------------------------------------ training (G update)
 extern "C" size_t damc_generator_train_workspace_bytes(const damc_generator_t* g, int B) {
-  if (validate(g) || B <= 0) return 0;
+  if (validate(g) || B <= 0 || train_supported(g, B)) return 0;
   return carve(g, B, nullptr, nullptr) + carve_train(g, B, nullptr, nullptr);
 }
 
@@ -1185,6 +1221,7 @@ static int setup_train(const damc_generator_t* g, int B, void* wsp, size_t wsb, 
   int rc = validate(g);
   if (rc) return rc;
   if (B <= 0) return DAMC_ERR_ARG;
+  if ((rc = train_supported(g, B))) return rc;
   const size_t n0 = carve(g, B, nullptr, nullptr);
   const size_t n1 = carve_train(g, B, nullptr, nullptr);
   if (!wsp || wsb < n0 + n1) return DAMC_ERR_WORKSPACE;

@@ -32,6 +32,8 @@ int launch_colsum2(const float* X, long R, int C, long ld, float* out_lo, float*
 // scratch (per-block partials in the PyTorch order, reduced by launch_colsum)
 size_t smallc_wgrad_part_floats(const damc_layer_t& L, int B);
 size_t smallc_wgrad_tmp_floats(const damc_layer_t& L, int B);
+// 0, or what launch_smallc_wgrad returns for this shape before it launches (the G update asks before its first launch)
+int smallc_wgrad_supported(const damc_layer_t& L, int B);
 int launch_smallc_wgrad(const damc_layer_t& L, const float* h, const float* delta, int B, float* part, float* tmp,
                         float* dW, hipStream_t s);
 

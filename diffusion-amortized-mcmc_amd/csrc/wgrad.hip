@@ -408,13 +408,23 @@ size_t smallc_wgrad_tmp_floats(const damc_layer_t& L, int B) {
   return colsum_tmp_floats(smallc_blocks(L, B), L.k * L.k * L.cout * L.cin);
 }
 
-int launch_smallc_wgrad(const damc_layer_t& L, const float* h, const float* delta, int B, float* part, float* tmp,
-                        float* dW, hipStream_t s) {
-  if (!h || !delta || !part || !dW || B <= 0) return DAMC_ERR_ARG;
+// by shape alone: an instantiation exists (Cout 1..4, k 3 or 4) and the gradient window fits in LDS
+int smallc_wgrad_supported(const damc_layer_t& L, int B) {
+  if (B <= 0) return DAMC_ERR_ARG;
+  if (L.cout < 1 || L.cout > 4 || (L.k != 3 && L.k != 4)) return DAMC_ERR_UNSUPPORTED;
   const int R = smallc_rows(L, B);
   const int Wd = L.stride * (L.win - 1) + L.k;
   const size_t sm = (size_t)(L.stride * (R - 1) + L.k) * Wd * L.cout * sizeof(float);
-  if (sm > 65536) return DAMC_ERR_UNSUPPORTED;
+  return sm > 65536 ? DAMC_ERR_UNSUPPORTED : 0;
+}
+
+int launch_smallc_wgrad(const damc_layer_t& L, const float* h, const float* delta, int B, float* part, float* tmp,
+                        float* dW, hipStream_t s) {
+  if (!h || !delta || !part || !dW || B <= 0) return DAMC_ERR_ARG;
+  if (int rc = smallc_wgrad_supported(L, B)) return rc;
+  const int R = smallc_rows(L, B);
+  const int Wd = L.stride * (L.win - 1) + L.k;
+  const size_t sm = (size_t)(L.stride * (R - 1) + L.k) * Wd * L.cout * sizeof(float);
   const int nrb = (L.hin + R - 1) / R;
   const dim3 grid((unsigned)nrb, (unsigned)B);
   const int T = L.k * L.k * L.cout;

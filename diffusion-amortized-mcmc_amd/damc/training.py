@@ -226,9 +226,24 @@ def _foreign_reparam(G):
                and _sn_hook(m) is None for m in seq)
 
 
+def _train_supported(plan, device, B):
+    """Whether the library takes this generator's G update at batch B: damc_generator_train_workspace_bytes is 0 for
+    what its backward would refuse (include/damc.h: a k4 s2 p1 layer whose Cout is no multiple of 8, ...).  By shape
+    and batch alone, so asked once per (plan, batch) on a descriptor that need not be packed yet."""
+    cache = plan.__dict__.setdefault("_train_ok", {})
+    ok = cache.get(B)
+    if ok is None:
+        device = torch.device(device)
+        if plan.desc is None or plan.device != device:
+            plan._alloc(device)
+        ok = cache[B] = int(_lib.lib().damc_generator_train_workspace_bytes(ctypes.byref(plan.desc), int(B))) > 0
+    return ok
+
+
 def generator_apply(G, z):
     """x_hat = G(z) on the HIP path, differentiable w.r.t. z and G's parameters.  None for a generator whose
-    reparametrised weights the library does not take (the caller then runs the stock modules)."""
+    reparametrised weights the library does not take, or whose G update it refuses (the caller then runs the stock
+    modules)."""
     if _foreign_reparam(G):
         return None
     plan = generator_plan(G)
@@ -244,7 +259,7 @@ def generator_apply(G, z):
         # the normalised weights; autograd composes its dL/dW_hat with damc_specnorm_backward onto weight_orig
         leaves = [p for m in plan.modules for p in m.parameters(recurse=False)]
         if torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in leaves)):
-            if specnorm_apply(sn) is None:
+            if not _train_supported(plan, z.device, z.shape[0]) or specnorm_apply(sn) is None:
                 return None
             with spectral_norm_preset():
                 return _GeneratorTrainFn.apply(z, plan, *[p for _, _, p in _params_of(plan)])
@@ -253,6 +268,8 @@ def generator_apply(G, z):
         return generator_forward(z.to(torch.float32).contiguous(), G)
     params = [p for _, _, p in _params_of(plan)]
     if torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in params)):
+        if not _train_supported(plan, z.device, z.shape[0]):
+            return None
         return _GeneratorTrainFn.apply(z, plan, *params)
     from .langevin import generator_forward
 

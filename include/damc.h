@@ -170,7 +170,12 @@ int damc_convT_dgrad(const damc_layer_t* layer, const float* gout, int batch, co
  * between: train_forward records (workspace, batch, engine) and train_backward returns DAMC_ERR_ARG for a
  * descriptor or batch that disagrees.  ConvT weight gradients run on the limb engine (fp32-accurate bf16
  * MFMA) whatever the layers' engine; layer inputs and gradients with a batch that is not a multiple of 32
- * are zero-padded to one. */
+ * are zero-padded to one.
+ * Generators the backward cannot run are refused on the host, before any launch: a k4 s2 p1 layer whose Cout, or a
+ * first layer whose Cout * k * k, is not a multiple of 8 (e.g. the celeba64 topology at ngf = 4: a last hidden layer
+ * of 4 channels), operands of a weight-gradient GEMM beyond 2^31 bytes, an output layer with k other than 3 or 4.
+ * damc_generator_train_workspace_bytes then returns 0 and both calls return DAMC_ERR_UNSUPPORTED; the plain forward
+ * (damc_generator_forward) and the Langevin entry points stay available for such a generator. */
 typedef struct {
   float* w[DAMC_MAX_LAYERS];
   float* b[DAMC_MAX_LAYERS];

@@ -67,6 +67,82 @@ def test_convT_hooks_match_fp64(gpu_device, ngf, layer):
     assert rel_l2(gin.cpu().numpy(), _nhwc(F.conv2d(gout.float().double(), w, stride=2, padding=1)).numpy()) < 1e-6
 
 
+@pytest.mark.parametrize("engine", ["limb", "fp32"])
+@pytest.mark.parametrize("cin,cout,hin,B", [(16, 8, 4, 3), (32, 8, 7, 2), (256, 64, 4, 4)])
+def test_convT_hooks_match_fp64_small_shapes(gpu_device, cin, cout, hin, B, engine):
+    """The same two hooks as test_convT_hooks_match_fp64 at the shapes the G update's parity cases run
+    (tests/gen_ops_util.py: 16 -> 8 off the limb engine, 32 -> 8 on a 7 x 7 grid, 256 -> 64 on a 4 x 4 grid
+    where K = 1024 splits), on both engines, into guarded buffers.  up2_hook_ok takes all three.  Bound: the project's
+    rule, |hip - fp64| <= 3 |torch fp32 (CPU) - fp64| + 1e-6 in rel-L2; on the limb engine also the 1e-6 of the test
+    above wherever the limb engine runs the GEMM."""
+    import encoder_ops_util as EU
+    from damc import _lib, plans, synth
+    from damc._lib import ptr
+
+    EU.reset_guards()
+    act = torch.nn.LeakyReLU(0.2)
+    seq = torch.nn.Sequential(torch.nn.ConvTranspose2d(8, cin, hin, 1, 0), act,
+                              torch.nn.ConvTranspose2d(cin, cout, 4, 2, 1), act,
+                              torch.nn.ConvTranspose2d(cout, 3, 3, 1, 1), torch.nn.Tanh())
+
+    class Holder(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.gen = seq
+
+    G = synth.load_into(Holder(), 7).to(gpu_device).eval()
+    eng = _lib.ENGINE_LIMB if engine == "limb" else _lib.ENGINE_FP32
+    gd = plans.generator_plan(G).refresh(gpu_device, engine=eng)
+    Ld = gd.layers[1]
+    conv = G.gen[2]
+    assert Ld.kind == _lib.LAYER_UP2 and (Ld.cin, Ld.cout, Ld.hin) == (cin, cout, hin)
+    g = torch.Generator().manual_seed(11 + cin + hin)
+    h = torch.randn(B, cin, hin, hin, generator=g)
+    gout = torch.randn(B, cout, 2 * hin, 2 * hin, generator=g)
+    w, b = conv.weight.detach().cpu(), conv.bias.detach().cpu()
+    L = _lib.lib()
+    nbytes = int(L.damc_convT_workspace_bytes(ctypes.byref(Ld), B))
+    assert nbytes > 0
+    ws = EU.guarded(nbytes, gpu_device)
+    stream = _lib.stream_ptr(gpu_device)
+    limb_fwd = engine == "limb" and cin % 32 == 0 and cout % 8 == 0
+    limb_bwd = engine == "limb" and cout % 32 == 0 and cin % 8 == 0
+
+    def both(fn):
+        return fn(torch.float32), fn(torch.float64)
+
+    hin_d = _nhwc(h).to(gpu_device)
+    out = EU.guarded((B, 2 * hin, 2 * hin, cout), gpu_device)
+    _lib.check(L.damc_convT_fwd(ctypes.byref(Ld), ptr(hin_d), B, ptr(out), ptr(ws), nbytes, stream), "convT_fwd")
+    EU.assert_guards_intact()
+    r32, r64 = both(lambda dt: _nhwc(F.leaky_relu(F.conv_transpose2d(h.to(dt), w.to(dt), b.to(dt), stride=2, padding=1),
+                                                  0.2)).numpy())
+    EU.check("convT_fwd %d-%d-%d-%d %s" % (cin, cout, hin, B, engine), out.cpu().numpy(), r32, r64, EU.CONV_SLICES)
+    if limb_fwd:
+        assert rel_l2(out.cpu().numpy(), r64) < 1e-6
+    gdev = _nhwc(gout).to(gpu_device)
+    for masked in (True, False):
+        gin = EU.guarded((B, hin, hin, cin), gpu_device)
+        mask = hin_d.clone()
+        _lib.check(L.damc_convT_dgrad(ctypes.byref(Ld), ptr(gdev), B, ptr(mask) if masked else None,
+                                      _lib.ACT_LRELU if masked else 0, 0.2 if masked else 0.0, ptr(gin), ptr(ws), nbytes,
+                                      stream), "convT_dgrad")
+        EU.assert_guards_intact()
+
+        def ref(dt):
+            v = F.conv2d(gout.to(dt), w.to(dt), stride=2, padding=1)
+            if masked:
+                v = v * torch.where(h.to(dt) > 0, 1.0, 0.2).to(dt)
+            return _nhwc(v).numpy()
+
+        r32, r64 = both(ref)
+        EU.check("convT_dgrad %d-%d-%d-%d %s %s" % (cin, cout, hin, B, engine, "masked" if masked else "plain"),
+                 gin.cpu().numpy(), r32, r64, EU.CONV_SLICES)
+        if limb_bwd:
+            assert rel_l2(gin.cpu().numpy(), r64) < 1e-6
+    EU.reset_guards()
+
+
 @pytest.mark.parametrize("name", Q_NAMES[:2])
 def test_denoise_steps_reproduce_the_sweep(gpu_device, name):
     """n single damc_denoise_step calls (injected noise, step index k) == one damc_q_reverse_sweep."""
