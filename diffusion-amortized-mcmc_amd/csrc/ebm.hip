@@ -114,10 +114,13 @@ __device__ void ebm_rows(const damc_ebm_t& e, EbmSmem& s, int nvalid, float* ene
   float* g2 = s.g2;
   float* g1 = s.g1;
   float* gz = s.gz;
-  // layer 1: a1 = W1 z + b1 ; h1 = lrelu(a1)      (w1t is (nz, nh))
+  // layer 1: a1 = W1 z + b1 ; h1 = lrelu(a1) ; g1 = lrelu'(a1), from the pre-activation as in the other two engines
+  // (h1's sign is a1's only for a positive slope); the layer-2 backward multiplies it in place      (w1t is (nz, nh))
   fc_rows<R>(e.w1t, nz, nh, s.zs, s.part, [&](int r, int j, float v) {
     v += b1[j];
-    h1[r * nh + j] = v > 0.f ? v : v * sl;
+    const bool pos = v > 0.f;
+    h1[r * nh + j] = pos ? v : v * sl;
+    g1[r * nh + j] = pos ? 1.f : sl;
   });
   // layer 2: a2 = W2 h1 + b2 ; h2 = lrelu(a2) ; g2 = w3 * lrelu'(a2)     (w2t is (nh, nh))
   fc_rows<R>(e.w2t, nh, nh, h1, s.part, [&](int r, int j, float v) {
@@ -137,9 +140,7 @@ __device__ void ebm_rows(const damc_ebm_t& e, EbmSmem& s, int nvalid, float* ene
     }
   }
   // layer 2 backward: g1 = (W2^T g2) * lrelu'(a1)      (w2 is (nh, nh) = [j][k])
-  fc_rows<R>(e.w2, nh, nh, g2, s.part, [&](int r, int k, float v) {
-    g1[r * nh + k] = h1[r * nh + k] > 0.f ? v : v * sl;
-  });
+  fc_rows<R>(e.w2, nh, nh, g2, s.part, [&](int r, int k, float v) { g1[r * nh + k] = mul_rn(v, g1[r * nh + k]); });
   // layer 1 backward: gz = W1^T g1                     (w1 is (nh, nz) = [j][c])
   fc_rows<R>(e.w1, nh, nz, g1, s.part, [&](int r, int c, float v) { gz[r * nz + c] = v; });
 }
@@ -665,7 +666,12 @@ __global__ __launch_bounds__(EB_THREADS) void ebm_reg_kernel(EbArgs a) {
 constexpr int EM_THREADS = 512, EM_WAVES = 8, EM_ROWS = 16;
 constexpr int EM_MAXW = 256;         // nz, nh <= 256
 constexpr int EM_LD = EM_MAXW + 4;   // LDS row stride (floats)
-bool ebm_mfma_ok(int nz, int nh) { return nz > 0 && nh > 0 && nz <= EM_MAXW && nh <= EM_MAXW && (nz & 15) == 0; }
+// nh % 4 == 0: em_tile reads f32x4 runs along K = nh of w2, w2t and w1t under the guard k < K alone, so a run that starts
+// inside a row has to end inside it (at nh = 201 the run at k = 200 would take three floats of the next row, and past the
+// end of the matrix for the last row)
+bool ebm_mfma_ok(int nz, int nh) {
+  return nz > 0 && nh > 0 && nz <= EM_MAXW && nh <= EM_MAXW && (nz & 15) == 0 && (nh & 3) == 0;
+}
 
 // acc[r] (row 4 (lane >> 4) + r, column n0 + (lane & 15)) of x[16][K] . W^T, W row n at w + n * ldw (k contiguous,
 // rows >= N and k >= K read as zero); x rows in LDS with stride EM_LD, zero-padded to a multiple of 16
@@ -817,7 +823,27 @@ bool ebm_shape_ok(int R, int nz, int nh) {
          ebm_smem_floats(R, nz, nh) * sizeof(float) <= 65536;
 }
 
+// The one dispatch of this file (damc_ebm_kernel): 1 = ebm_reg_kernel, 2 = prior_chain_mfma_kernel, 3 = the streaming
+// kernels on ebm_rows, 0 = none.  engine 0 / 1 / 2: a prior chain of that engine and batch; engine -1: the energy /
+// gradient call and the posterior update (nh = 0: the update without an EBM).
+static_assert(RP == RU, "one LDS bound for the streaming kernels");
+int ebm_kernel_of(int nz, int nh, int engine, int batch) {
+  if (engine < -1 || engine > 2) return 0;
+  if (engine == -1) {
+    if (ebm_reg_ok(nz, nh)) return 1;
+    return ebm_shape_ok(RU, nz, nh) ? 3 : 0;
+  }
+  if (nh <= 0) return 0;
+  const bool mfma = ebm_mfma_ok(nz, nh);
+  if (engine == 2) return mfma ? 2 : 0;
+  if (engine == 0 && mfma && batch >= damc_ebm_mfma_min_chains()) return 2;
+  if (ebm_reg_ok(nz, nh)) return 1;
+  return ebm_shape_ok(RP, nz, nh) ? 3 : 0;
+}
+
 }  // namespace
+
+extern "C" int damc_ebm_kernel(int nz, int nh, int engine, int batch) { return ebm_kernel_of(nz, nh, engine, batch); }
 
 // host helpers used by generator.hip
 // the register-resident update kernel runs (and can sum split-K slabs and write z's limbs itself) for this EBM
@@ -836,7 +862,8 @@ int damc_launch_posterior_update(const damc_ebm_t* e, float* z, const float* sla
     if (ev.nz != nz) return DAMC_ERR_ARG;
   }
   const float c1 = (float)(0.5 * step * step);  // float32(0.5 * s * s), the reference's scalar
-  if (use_ebm && ebm_reg_ok(nz, ev.nh)) {
+  const int kern = damc_ebm_kernel(nz, use_ebm ? ev.nh : 0, -1, B);
+  if (kern == 1) {
     EbArgs a{};
     a.e = ev;
     a.z = z;
@@ -860,7 +887,7 @@ int damc_launch_posterior_update(const damc_ebm_t* e, float* z, const float* sla
     hipLaunchKernelGGL(ebm_reg_kernel<EB_POSTERIOR>, dim3(B), dim3(EB_THREADS), 0, s, a);
     return (int)hipGetLastError();
   }
-  if (!ebm_shape_ok(RU, nz, use_ebm ? ev.nh : 0)) return DAMC_ERR_UNSUPPORTED;
+  if (kern != 3) return DAMC_ERR_UNSUPPORTED;
   const size_t sm = ebm_smem_floats(RU, nz, use_ebm ? ev.nh : 0) * sizeof(float);
   ProfScope ps("posterior_update", 0.0, s);
   hipLaunchKernelGGL((posterior_update_kernel<RU>), dim3((B + RU - 1) / RU), dim3(EBM_THREADS), sm, s, ev, use_ebm, z, slabs,
@@ -888,12 +915,12 @@ static int prior_langevin_impl(const damc_ebm_t* e, float* z, int B, int n_steps
   if (!e || !z || B <= 0 || n_steps < 0) return DAMC_ERR_ARG;
   if (!e->w1t || !e->w2t) return DAMC_ERR_ARG;
   hipStream_t s = as_stream(stream);
+  const int kern = damc_ebm_kernel(e->nz, e->nh, engine, B);
+  if (kern == 0) return DAMC_ERR_UNSUPPORTED;  // before the memset: a refused call touches nothing
   if (diag) DAMC_CHECK(hipMemsetAsync(diag, 0, sizeof(float) * 2 * (size_t)n_steps, s));
   if (n_steps == 0) return 0;
   const float c1 = (float)(0.5 * step * step);  // float32(0.5 * s * s), the reference's scalar
-  const int mfma_min_b = damc_ebm_mfma_min_chains();
-  if (engine == 2 && !ebm_mfma_ok(e->nz, e->nh)) return DAMC_ERR_UNSUPPORTED;
-  if (ebm_mfma_ok(e->nz, e->nh) && (engine == 2 || (engine == 0 && B >= mfma_min_b))) {
+  if (kern == 2) {
     EbArgs a{};
     a.e = *e;
     a.z = z;
@@ -912,7 +939,7 @@ static int prior_langevin_impl(const damc_ebm_t* e, float* z, int B, int n_steps
     hipLaunchKernelGGL(prior_chain_mfma_kernel, dim3((B + EM_ROWS - 1) / EM_ROWS), dim3(EM_THREADS), 0, s, a);
     return (int)hipGetLastError();
   }
-  if (ebm_reg_ok(e->nz, e->nh)) {
+  if (kern == 1) {
     EbArgs a{};
     a.e = *e;
     a.z = z;
@@ -931,7 +958,6 @@ static int prior_langevin_impl(const damc_ebm_t* e, float* z, int B, int n_steps
     hipLaunchKernelGGL(ebm_reg_kernel<EB_PRIOR>, dim3(B), dim3(EB_THREADS), 0, s, a);
     return (int)hipGetLastError();
   }
-  if (!ebm_shape_ok(RP, e->nz, e->nh)) return DAMC_ERR_UNSUPPORTED;
   const size_t sm = ebm_smem_floats(RP, e->nz, e->nh) * sizeof(float);
   ProfScope ps("prior_chain", 4.0 * (double)B * n_steps * ((double)e->nz * e->nh + (double)e->nh * e->nh), s);
   hipLaunchKernelGGL((prior_chain_kernel<RP>), dim3((B + RP - 1) / RP), dim3(EBM_THREADS), sm, s, *e, z, B, n_steps, c1, (float)step,
@@ -970,8 +996,10 @@ extern "C" int damc_draw_state_advance(damc_draw_state_t* state, uint64_t delta,
 
 extern "C" int damc_ebm_energy_grad(const damc_ebm_t* e, const float* z, int B, float* energy, float* grad,
                                     void* stream) {
-  if (!e || !z || !grad || B <= 0) return DAMC_ERR_ARG;
-  if (ebm_reg_ok(e->nz, e->nh)) {
+  if (!e || !z || !grad || B <= 0 || e->nh <= 0) return DAMC_ERR_ARG;
+  const int kern = damc_ebm_kernel(e->nz, e->nh, -1, B);
+  if (kern == 0) return DAMC_ERR_UNSUPPORTED;
+  if (kern == 1) {
     EbArgs a{};
     a.e = *e;
     a.z = const_cast<float*>(z);
@@ -981,7 +1009,6 @@ extern "C" int damc_ebm_energy_grad(const damc_ebm_t* e, const float* z, int B, 
     hipLaunchKernelGGL(ebm_reg_kernel<EB_GRAD>, dim3(B), dim3(EB_THREADS), 0, as_stream(stream), a);
     return (int)hipGetLastError();
   }
-  if (!ebm_shape_ok(RP, e->nz, e->nh)) return DAMC_ERR_UNSUPPORTED;
   const size_t sm = ebm_smem_floats(RP, e->nz, e->nh) * sizeof(float);
   hipLaunchKernelGGL((ebm_energy_grad_kernel<RP>), dim3((B + RP - 1) / RP), dim3(EBM_THREADS), sm, as_stream(stream), *e, z, B,
                      energy, grad);
@@ -1009,6 +1036,27 @@ extern "C" int damc_z_update_ds(float* z, const float* g, int B, int nz, double 
                                 uint64_t chain_base, void* stream) {
   if (!state) return DAMC_ERR_ARG;
   return z_update_impl(z, g, B, nz, step, with_noise, noise, 0, step_index, chain_base, stream, state);
+}
+
+// per-op hook: the posterior step's update launch on its own (damc.h); every refusal is on the host
+extern "C" int damc_posterior_update(const damc_ebm_t* ebm, float* z, const float* glik_slabs, int nslab,
+                                     long slab_stride, int B, int nz, double step, int with_noise, const float* noise,
+                                     uint64_t seed, uint64_t step_index, uint64_t chain_base, float* diag,
+                                     unsigned short* z_limbs, int* limbs_written, void* stream) {
+  if (limbs_written) *limbs_written = 0;
+  if (!z || !glik_slabs || !limbs_written || B <= 0 || nz <= 0 || nslab < 1) return DAMC_ERR_ARG;
+  if (nslab > 1 && slab_stride < (long)B * nz) return DAMC_ERR_ARG;
+  if (ebm && (ebm->nz != nz || ebm->nh <= 0 || !ebm->w1 || !ebm->b1 || !ebm->w2 || !ebm->b2 || !ebm->w3 || !ebm->b3 ||
+              !ebm->w1t || !ebm->w2t))
+    return DAMC_ERR_ARG;
+  if (damc_ebm_kernel(nz, ebm ? ebm->nh : 0, -1, B) == 0) return DAMC_ERR_UNSUPPORTED;
+  hipStream_t s = as_stream(stream);
+  if (diag) DAMC_CHECK(hipMemsetAsync(diag, 0, sizeof(float) * 4, s));
+  bool wrote = false;
+  const int rc = damc_launch_posterior_update(ebm, z, glik_slabs, nslab, slab_stride, B, nz, step, with_noise, noise,
+                                              seed, step_index, chain_base, diag, s, z_limbs, &wrote, nullptr);
+  *limbs_written = wrote ? 1 : 0;
+  return rc;
 }
 
 static int philox_normal_impl(float* out, int n_steps, int B, int nz, uint64_t seed, uint64_t step_offset,

@@ -210,6 +210,9 @@ _SIGS = {
     "damc_ebm_mfma_min_chains": (_I, []),
     "damc_ebm_energy_grad": (_I, [ctypes.POINTER(Ebm), _P, _I, _P, _P, _P]),
     "damc_z_update": (_I, [_P, _P, _I, _I, _D, _I, _P, _U64, _U64, _U64, _P]),
+    "damc_ebm_kernel": (_I, [_I, _I, _I, _I]),
+    "damc_posterior_update": (_I, [ctypes.POINTER(Ebm), _P, _P, _I, ctypes.c_long, _I, _I, _D, _I, _P, _U64, _U64, _U64,
+                                   _P, _P, ctypes.POINTER(_I), _P]),
     "damc_philox_normal": (_I, [_P, _I, _I, _I, _U64, _U64, _U64, ctypes.c_uint32, _P]),
     "damc_philox_uniform": (_I, [_P, _I, _I, _U64, _U64, _U64, ctypes.c_uint32, _P]),
     "damc_recon_rows_workspace_bytes": (_SZ, [_I, ctypes.c_long]),

@@ -85,7 +85,8 @@ def posterior_langevin(z, x, netG, netE, n_steps, sigma, step, with_noise, noise
         raise _lib.DamcError("posterior_langevin(draws=...): train-mode spectral-norm chains run one host-driven power "
                              "iteration per step and cannot be replayed from a graph; use seed=")
     # train-mode spectral norm: netG(z) and netE(z) once per reference step (MCMC.py:54-58), one power iteration each
-    nzs = noise.view(-1, B * gp.nz) if noise is not None else None
+    # a longer buffer is accepted as on the one-call path: the first n_steps * B * nz values are the noise
+    nzs = noise.view(-1)[:int(n_steps) * B * gp.nz].view(int(n_steps), B * gp.nz) if noise is not None else None
     for i in range(int(n_steps)):
         with spectral_norm_step(sn):
             run(1, step_offset + i, nzs[i] if nzs is not None else None, dg[i] if dg is not None else None)
@@ -185,7 +186,8 @@ def prior_langevin(z, netE, n_steps, step, with_noise, noise=None, seed=None, st
         raise _lib.DamcError("prior_langevin(draws=...): train-mode spectral-norm chains run one host-driven power "
                              "iteration per step and cannot be replayed from a graph; use seed=")
     # train-mode spectral norm: netE(z) once per reference step (MCMC.py:32), one power iteration each
-    nzs = noise.view(-1, B * ep.nz) if noise is not None else None
+    # a longer buffer is accepted as on the one-call path: the first n_steps * B * nz values are the noise
+    nzs = noise.view(-1)[:int(n_steps) * B * ep.nz].view(int(n_steps), B * ep.nz) if noise is not None else None
     for i in range(int(n_steps)):
         with spectral_norm_step(sn):
             run(1, step_offset + i, nzs[i] if nzs is not None else None, dg[i] if dg is not None else None)

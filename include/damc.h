@@ -195,7 +195,9 @@ int damc_prior_langevin(const damc_ebm_t* ebm, float* z, int batch, int n_steps,
                         float* diag, void* stream);
 /* the same with the engine chosen per call: 0 = by batch size (the default above: the 16-chain MFMA tile kernel
  * from DAMC_EBM_MFMA_MIN_B = 2048 chains up, where the FC layers are real GEMMs), 1 = register-resident VALU
- * (one chain per workgroup), 2 = MFMA (nz % 16 == 0, nz and nh <= 256, else DAMC_ERR_UNSUPPORTED).
+ * (one chain per workgroup), 2 = MFMA (nz % 16 == 0, nh % 4 == 0, nz and nh <= 256, else DAMC_ERR_UNSUPPORTED: the
+ * tile reads its weight rows as float4 runs along nh, and a run that starts inside a row must end inside it; engine 0
+ * takes the VALU kernels for such a shape at any batch).
  * Engine 0 is keyed on THIS call's batch.  The two engines sum in different orders, so a sharded caller that needs
  * its shards' union bitwise equal to the unsharded block resolves the engine itself from the global chain count
  * (>= damc_ebm_mfma_min_chains() -> 2, else 1) and passes 1 or 2, as damc.langevin does. */
@@ -218,6 +220,30 @@ int damc_z_update(float* z, const float* g, int batch, int nz, double step, int 
                   uint64_t seed, uint64_t step_index, uint64_t chain_base, void* stream);
 int damc_z_update_ds(float* z, const float* g, int batch, int nz, double step, int with_noise, const float* noise,
                      const damc_draw_state_t* state, uint64_t step_index, uint64_t chain_base, void* stream);
+/* Which kernel of csrc/ebm.hip a call runs, by shape, engine and batch alone (host only, no launch):
+ *   1 = register-resident VALU (nz <= 128 and nh <= 208), 2 = MFMA tile, 3 = streaming (every other shape whose
+ *   rows fit 64 KB of LDS), 0 = none: the call returns DAMC_ERR_UNSUPPORTED.
+ * engine 0 / 1 / 2: a prior chain of damc_prior_langevin_engine with that engine and batch.  engine -1: the choice of
+ * damc_ebm_energy_grad and of the posterior update (1, 3 or 0; batch is not read; nh = 0 asks for the update without
+ * an EBM).  The entry points dispatch through this function. */
+int damc_ebm_kernel(int nz, int nh, int engine, int batch);
+/* per-op hook: the update kernel of one posterior Langevin step, exactly what damc_posterior_langevin launches after
+ * the likelihood gradient and nothing else:
+ *   g = sum_k glik_slabs[k * slab_stride + i] (+ grad_z E(z) when ebm != NULL) + z ; z <- z - 0.5 step^2 g (+ step xi)
+ * z (batch, nz) in place; glik_slabs: nslab >= 1 slabs of (batch, nz), slab k at glik_slabs + k * slab_stride
+ * (slab_stride >= batch * nz when nslab > 1).  The register-resident kernel adds the slabs in 16 groups of every 16th
+ * slab and then the groups in order, the streaming kernel in slab order.  xi: noise (batch, nz) when given, else the
+ * Philox draw of (seed, chain_base + row, step_index) on the posterior stream.  diag (optional, 4 floats, zeroed by
+ * the call): {sum E, untouched (0), |z|^2/2, mean(g)} before the update.  z_limbs (optional, batch * nz * 3 bf16): the
+ * new z as x3 limbs [batch][nz / 8][3][8]; *limbs_written (required) is 1 when the kernel wrote them (the
+ * register-resident kernel at nz % 8 == 0), else 0 and z_limbs is untouched.  NULL z, glik_slabs or limbs_written,
+ * batch, nz or nslab < 1, an ebm whose nz differs, that lacks a pointer, or a slab_stride below batch * nz with
+ * nslab > 1 return DAMC_ERR_ARG before any launch; a shape with damc_ebm_kernel(nz, nh, -1, 0) == 0 returns
+ * DAMC_ERR_UNSUPPORTED. */
+int damc_posterior_update(const damc_ebm_t* ebm, float* z, const float* glik_slabs, int nslab, long slab_stride,
+                          int batch, int nz, double step, int with_noise, const float* noise, uint64_t seed,
+                          uint64_t step_index, uint64_t chain_base, float* diag, unsigned short* z_limbs,
+                          int* limbs_written, void* stream);
 /* Philox N(0,1) draw used by every Langevin kernel (statistical tests) -> out (n_steps,B,nz) */
 int damc_philox_normal(float* out, int n_steps, int batch, int nz, uint64_t seed, uint64_t step_offset,
                        uint64_t chain_base, uint32_t stream_id, void* stream);
