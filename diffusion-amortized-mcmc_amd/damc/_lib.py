@@ -157,6 +157,7 @@ class AdamCapturable(ctypes.Structure):  # damc_adam_capturable_t
 
 ADAM_CHUNK = 8192
 ADAM_MAX_TENSORS = 96
+LR_DECAY_MAX = 8  # DAMC_LR_DECAY_MAX
 
 
 _P = ctypes.c_void_p
@@ -273,6 +274,10 @@ _SIGS = {
     "damc_grad_pack": (_I, [_P, _I, _P, ctypes.POINTER(ctypes.c_longlong), _I, _F, _P, _P]),
     "damc_adam_step": (_I, [_P, _I, _P, _P, _P, _P, _I, ctypes.POINTER(AdamHparams), _P, _P]),
     "damc_adam_step_capturable": (_I, [_P, _I, _P, _P, _P, _P, _I, ctypes.POINTER(AdamCapturable), _P, _I, _P, _P, _P]),
+    # the iteration glue (csrc/schedule.hip): counter, device-gated EMA and lr decay
+    "damc_iteration_advance": (_I, [_P, _U64, _P]),
+    "damc_ema_update": (_I, [_P, _I, _P, _P, _I, _F, _F, _P, _U64, _U64, _P]),
+    "damc_lr_decay": (_I, [_P, _P, _I, _D, _D, _P, _U64, _U64, _P]),
     # the drawn variants: a damc_draw_state_t* (device memory) where the seeded entry point takes its uint64 seed
     "damc_draw_state_advance": (_I, [_P, _U64, _P]),
     "damc_posterior_langevin_ds": (_I, [ctypes.POINTER(Generator), ctypes.POINTER(Ebm), _P, _P, _I, _I, _D, _D, _I, _P,

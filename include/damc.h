@@ -766,6 +766,32 @@ int damc_adam_step_capturable(const void* dev_chunks, int nchunks, float* const*
                               const damc_adam_capturable_t* hp, float* step, int advance, const float* lr,
                               const float* clip, void* stream);
 
+/* --------------------------------------------------- iteration glue: counter, EMA target, lr decay (schedule.hip)
+ * What the reference driver runs on the host between its updates (train_gen_recon.py:247-261), as launches gated by an
+ * iteration count in DEVICE memory, so a HIP graph of a whole iteration takes the "every Nth iteration" branches on
+ * the replays that are due.  `iteration` is one uint64 word; a gated call applies when
+ *   (*iteration + phase) % period == 0          (the reference's `(iteration + 1) % 10 == 0`: period 10, phase 1)
+ * and otherwise writes NOTHING (a uniform early exit of the grid); iteration == NULL applies always.  The word is
+ * written by damc_iteration_advance alone, in a launch of its own.  All three are stream-ordered and capturable, do not
+ * allocate and do not synchronise.  They return -DAMC_ERR_ARG on the host, before any launch, for a NULL iteration
+ * (advance), NULL tables or pointer arrays or entries, ntensors outside 1..DAMC_ADAM_MAX_TENSORS, n outside
+ * 1..DAMC_LR_DECAY_MAX, period == 0; otherwise 0 or a hipError_t. */
+#define DAMC_LR_DECAY_MAX 8
+/* *iteration += delta (a one-thread kernel) */
+int damc_iteration_advance(uint64_t* iteration, uint64_t delta, void* stream);
+/* target[t][i] = fl(fl(rho * source[t][i]) + fl(one_minus_rho * target[t][i])) over the chunk table of the tensors'
+ * sizes (damc_adam_build_chunks): two rounded products and one rounded add, bitwise torch's
+ * `rho * p + (1 - rho) * t` in fp32.  target / source: host arrays of ntensors device pointers that travel in the
+ * kernel arguments.  16-byte accesses where a chunk's target and source are both 16-byte aligned, scalar ones
+ * otherwise and for the tail (the same values).  source is only read.  12 B per element. */
+int damc_ema_update(const void* dev_chunks, int nchunks, float* const* target, const float* const* source,
+                    int ntensors, float rho, float one_minus_rho, const uint64_t* iteration, uint64_t period,
+                    uint64_t phase, void* stream);
+/* lr64[i] = fmax(lr64[i] * factor, floor) in IEEE double (Python's max(lr * factor, floor)), then
+ * lr32[i] = (float)lr64[i], for i < n: lr32[i] is the device scalar damc_adam_step_capturable reads as `lr`. */
+int damc_lr_decay(double* lr64, float* lr32, int n, double factor, double floor, const uint64_t* iteration,
+                  uint64_t period, uint64_t phase, void* stream);
+
 /* ------------------------------------------------------------ FID statistics */
 /* calculate_fid* (workspace/src/MCMC.py:130-176) reduce Inception pool features to (mu, sigma) before the
  * Frechet distance (pytorch-fid's calculate_frechet_distance, via pfw.fid).  Here the statistics accumulate on
