@@ -615,7 +615,7 @@ __global__ __launch_bounds__(EB_THREADS) void ebm_reg_kernel(EbArgs a) {
         float zn = sub_rn(zv, mul_rn(a.c1, g));
         if (a.with_noise) zn = add_rn(zn, mul_rn(a.step, xs[tid]));
         zs[tid] = zn;
-        if (MODE == EB_POSTERIOR && a.z3) {  // RNE limbs (gemm.hip split3_octet's arithmetic), x3 octet layout
+        if (MODE == EB_POSTERIOR && a.z3) {  // RNE limbs (gemm_impl.h split3_octet's arithmetic), x3 octet layout
           const __bf16 b0 = (__bf16)zn;
           const float r1 = sub_rn(zn, (float)b0);
           const __bf16 b1 = (__bf16)r1;

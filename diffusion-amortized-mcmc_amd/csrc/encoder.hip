@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void in_apply_f32_kernel(float* y, long n4, in
 // keeps InstanceNorm's own operation order instead), written as the next convolution's limbs (x3
 // octets) instead of fp32 in place: the limb engine reads nothing else.  One thread per (pixel, channel octet).
 // y32 != NULL: fp32 in place instead (y32 == y; every thread rewrites only the octet it read), for a next conv that
-// stages its input as fp32 (gemm.hip X3_F32A)
+// stages its input as fp32 (gemm_x3.hip X3_F32A)
 __global__ __launch_bounds__(256) void in_apply_x3_kernel(const float* y, long n8, int HW, int C,
                                                           const float* __restrict__ ss, float slope,
                                                           unsigned short* __restrict__ y3, float* y32) {
@@ -822,7 +822,7 @@ __global__ __launch_bounds__(512) void conv3_in_fused_kernel(const float* __rest
 // in_apply_x3_kernel's normalise + LReLU + limb store.  Replaces in_stats + in_merge + in_apply_x3 (one read of the
 // activation instead of two, one launch instead of three).
 template <int NIT>
-// y32 != NULL: the result leaves as fp32 NHWC at y32 instead of limbs (the next conv stages it as fp32, gemm.hip
+// y32 != NULL: the result leaves as fp32 NHWC at y32 instead of limbs (the next conv stages it as fp32, gemm_x3.hip
 // X3_F32A); y32 may be y itself (every thread writes only the elements it read, after both block sums); chw: fp32 in
 // CHW order per sample instead (the dense head's input; y32 must then be another buffer)
 // slab != NULL: y was not written; the conv's ks split-K slabs (register layout of the 256 x 128 limb tiles, as

@@ -56,7 +56,7 @@ damc_layer_t up_view(int hin, int win, int cin, int cout, int ho, int wo) {
   return L;
 }
 
-// limb-engine capability of the transposed view's forward (gemm.hip launch_gemm_x3 constraints)
+// limb-engine capability of the transposed view's forward (gemm_x3.hip launch_gemm_x3 constraints)
 bool up_x3(int cin, int cout) { return cout % KM_BK == 0 && cin % 8 == 0; }
 
 int up_split(int ho, int wo, int cin, int cout, int Bp, int* S, int* kper) {
@@ -282,7 +282,7 @@ int backward_up(const float* x, const float* dy, const float* w, int B, int hin,
   a.Wout = win;
   a.act = DAMC_ACT_NONE;
   if (up_x3(cin, cout)) {
-    // dy staged as fp32 and split into limbs in registers (gemm.hip X3_F32A; bitwise the limb copy, no split launch);
+    // dy staged as fp32 and split into limbs in registers (gemm_x3.hip X3_F32A; bitwise the limb copy, no split launch);
     // DAMC_ENC_BWD_F32A=0 (read per call) gathers the limbs of launch_split_x3
     const char* ef = getenv("DAMC_ENC_BWD_F32A");
     if (!(ef && ef[0] == '0')) {

@@ -1,4 +1,5 @@
-// gemm.h — host interface of the fp32 MFMA implicit-GEMM engine (gemm.hip).
+// gemm.h — host interface of the three GEMM engines (generic fp32 MFMA: gemm.hip; K-major conv: gemm_km.hip; bf16
+// limb "x3": gemm_x3.hip, x3_pack.hip) and the device helpers their callers share (limb split, norm statistics).
 #pragma once
 #include <cstdlib>
 #include "common.h"
@@ -57,7 +58,7 @@ struct GemmArgs {
   float* sqerr = nullptr;       // EPI_RESID: accumulates |t - x|^2 * inv_s2 / 2 (diagnostics)
   int Hout = 1, Wout = 1;
   int b_kmajor = 0;
-  // limb engine (gemm_x3_kernel): A and B as x3 bf16 limb tensors (see gemm.hip); when A3 is set the
+  // limb engine (gemm_x3_kernel): A and B as x3 bf16 limb tensors (see gemm_x3.hip); when A3 is set the
   // fp32 A / B pointers are not read
   const unsigned short* A3 = nullptr;
   const unsigned short* B3 = nullptr;
@@ -73,7 +74,7 @@ struct GemmArgs {
   // hyper bias computed by one GEMM, diffusion_net.py:441-443)
   int gate_cols = 0;
   // limb engine: B3 holds -B on the odd blocks of negk consecutive k of every row (launch_split_x3_negblk),
-  // and the kernel subtracts those blocks' sums (the MFMA's truncation bias then alternates sign; gemm.hip)
+  // and the kernel subtracts those blocks' sums (the MFMA's truncation bias then alternates sign; gemm_x3.hip)
   int b_negblk = 0;
   // limb engine: k per sign block = per MFMA accumulation block = per split-K slab (a power of two >= 32); the
   // packer of B3 and every launch reading it use the same value (generator.hip up2_negk: 512 or 1024 per layer)
@@ -86,7 +87,7 @@ struct GemmArgs {
   int a_f32 = 0;
   // host pointer (EPI_BIAS_ACT, O_DENSE, no C3 / sgn): when set and the launch splits K into register-layout slabs
   // (kslab_reg), the reduce is skipped and the slab count is written here for a consumer that sums the slabs itself
-  // (the encoder's InstanceNorm; slab layout: gemm.hip x3_ksplit_reduce_tile_kernel); 0 = the launcher reduced or did
+  // (the encoder's InstanceNorm; slab layout: gemm_x3.hip x3_ksplit_reduce_tile_kernel); 0 = the launcher reduced or did
   // not split, C holds the result
   int* ksplit_deferred = nullptr;
   // clock probe (damc_clock_probe; diagnostics, off in timed work): thread 0 of each workgroup stores {s_memtime,
@@ -100,7 +101,7 @@ struct GemmArgs {
   const float* proj_w = nullptr;
   float* proj_out = nullptr;
   int proj_np = 0, proj_ldw = 0, proj_nostore = 0;
-  // one chain per 128-channel chunk (gemm.hip PROJ_CHUNK), chunk j into proj_out + j * proj_pstride (floats; the whole
+  // one chain per 128-channel chunk (PROJ_CHUNK), chunk j into proj_out + j * proj_pstride (floats; the whole
   // batch's npix * proj_np); the gather adds the partials in order
   long proj_pstride = 0;
   // limb engine, O_PHASE / O_DENSE: split-K over ksplit slices of k_per_z (a multiple of X3_NEGK) when the grid
@@ -121,7 +122,7 @@ struct GemmArgs {
   // (x3_conv_walk for the encoder's convs, x3_up2_walk for the generator's k4 s2 layers); 0 = tap-major
   int kwalk = 0;
   // limb engine, F32A with kwalk (round 7): 1 = the launcher may stage one fp32 input image per group of four K tiles
-  // (gemm.hip X3_TAPSHARE) where the geometry allows it (x3_tapshare_ok); bitwise the per-tap staging
+  // (gemm_x3.hip X3_TAPSHARE) where the geometry allows it (x3_tapshare_ok); bitwise the per-tap staging
   int tapshare = 0;
   // InstanceNorm statistics of the epilogue result (round 6; limb engine, O_DENSE, EPI_BIAS_ACT, unsplit 256 x 128
   // tiles: the encoder's norms): per (sample, 256-row strip, channel) {n, mean, m2} at
@@ -228,7 +229,7 @@ inline int x3_conv_negk(long m_per_sample, int N, int K, int zdim) {
 // block: slice-major whenever the gathered channel count is whole 32-channel slices (every layer the limb engine
 // takes).  cg = the forward's cin (rows of 4 cin per phase: [c / 32][tap][c % 32], launch_split_x3_cmaj's order) or
 // the input gradient's cout (rows of 16 cout: the x3_conv_walk order).  The four K tiles of a group (slice, parity
-// class) then read one input image displaced by 0 / 1 grid positions, which the F32A loop stages once (gemm.hip
+// class) then read one input image displaced by 0 / 1 grid positions, which the F32A loop stages once (gemm_x3.hip
 // X3_TAPSHARE).  Every packer and every launch of a call reads this rule; the fp32 copies keep their layout
 inline int x3_up2_walk(int cg) { return (cg > 0 && cg % 32 == 0) ? 1 : 0; }
 // whether a slice-major F32A launch on an Hq x Wq output grid stages one image per group: a 256-row M tile must hold
@@ -299,7 +300,9 @@ int pack_conv_x3_many_prep(PackConvList& l);
 int launch_pack_conv_x3_many(PackConvList l, hipStream_t s);
 
 // the limb form of 8 consecutive fp32 values (the engine's RNE split: v = hi + mid + lo to 24 significand bits),
-// stored as one x3 octet [3][8] bf16 at dst (16-B aligned)
+// stored as one x3 octet [3][8] bf16 at dst (16-B aligned).  The arithmetic of gemm_impl.h split3_octet, spelled a
+// second time: with either spelling serving both, hipcc schedules the other's kernels differently
+// (profiles/r22/isa_identity.txt)
 __device__ __forceinline__ void store_x3_octet(const float (&v)[8], unsigned short* dst) {
   typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
   bf16x8_t h, m, l;
@@ -319,7 +322,7 @@ __device__ __forceinline__ void store_x3_octet(const float (&v)[8], unsigned sho
 }
 
 // one workgroup (nthr threads, pk_t = CC * (taps + 1) floats of LDS) of the LDS-transposing conv weight packing
-// (gemm.hip pack_conv_x3_lds_kernel; also run by the encoder's first-layer kernel as extra workgroups): workgroup blk
+// (x3_pack.hip pack_conv_x3_lds_kernel; also run by the encoder's first-layer kernel as extra workgroups): workgroup blk
 // of a prepared list = (layer, co, chunk of CC input channels).  The chunk's CC * k * k floats are one contiguous run
 // of the PyTorch layout (read as f32x4), transposed in LDS to (tap, channel); each tap's CC / 8 limb octets are
 // CC * 6 contiguous bytes of the K-major output, odd sign blocks negated

@@ -212,7 +212,7 @@ int proj_slices(long K) {
 // slice length: a multiple of the K-major engine's K tile (depends on K only, never on the batch)
 int proj_k_per(long K, int S) { return (int)(((K + S - 1) / S + 31) / 32 * 32); }
 
-// Limb engine (gemm.hip, fp32-accurate bf16 MFMA) for the UP2 convolutions whose gathered channel
+// Limb engine (gemm_x3.hip, fp32-accurate bf16 MFMA) for the UP2 convolutions whose gathered channel
 // count is a multiple of 32.  Packed weights and workspaces always carry the x3 copies such a layer
 // can use; a descriptor whose layers say engine = DAMC_ENGINE_FP32 routes the launches to the fp32-MFMA
 // K-major engine instead.  The choice travels in the descriptor (no process-global state), so two
@@ -412,7 +412,7 @@ double conv_flops(const damc_layer_t& L, int B) {
 
 // forward of layers [0, n-1) into ws.h; returns 0 on success.  z3_ready: ws.z3 already holds z's limbs (the previous
 // posterior update wrote them)
-// f32a: limb-engine convolutions gather their input as fp32 (gemm.hip X3_F32A), so every activation is stored fp32
+// f32a: limb-engine convolutions gather their input as fp32 (gemm_x3.hip X3_F32A), so every activation is stored fp32
 // and no limb copy is written
 // proj: the last hidden layer's epilogue also runs the output layer's projection into ws.pbuf (proj_fusable)
 int forward_hidden(const damc_generator_t* g, const float* z, int B, Workspace& ws, hipStream_t s,
@@ -716,7 +716,7 @@ int backward(const damc_generator_t* g, int B, Workspace& ws, hipStream_t s, boo
 // The G update of a training iteration (workspace/train_gen_recon.py:222-231): after the forward above,
 // dL/dx_hat -> per-layer dL/dW, dL/db (and optionally dL/dz).  Layer i's weight gradient is taken before
 // its input gradient overwrites the activation buffers it reads.  k4 s2 p1 and first-layer weight
-// gradients run on the limb engine (gemm.hip O_WGRAD) over pixel-major transposes (wgrad.hip) of the layer
+// gradients run on the limb engine (gemm_x3.hip O_WGRAD) over pixel-major transposes (wgrad.hip) of the layer
 // input and of the pre-activation gradient, the latter split into the 4 output phases; batches are padded
 // to Bp = a multiple of 32 samples with zeros.
 struct TrainWs {
@@ -1105,7 +1105,7 @@ extern "C" int damc_convT_fwd(const damc_layer_t* L, const float* in, int B, flo
   a.A = in;
   int rc;
   if (x3_fwd(*L)) {
-    // the fp32 input gathered as it is (gemm.hip X3_F32A), as inside the Langevin step; DAMC_X3_F32A=0 (read per call)
+    // the fp32 input gathered as it is (gemm_x3.hip X3_F32A), as inside the Langevin step; DAMC_X3_F32A=0 (read per call)
     // gathers a limb copy (bitwise the same)
     if (hook_f32a(in)) {
       a.a_f32 = 1;
@@ -1161,7 +1161,7 @@ static int posterior_langevin_impl(const damc_generator_t* g, const damc_ebm_t* 
   // z's limbs for the next step's first layer; DAMC_POST_FUSE=0 (read per call) keeps the separate kernels
   const char* pf = getenv("DAMC_POST_FUSE");
   const bool fuse = !(pf && pf[0] == '0');
-  // the limb-engine convolutions gather fp32 activations and gradients (gemm.hip X3_F32A), bitwise the limb-gathering
+  // the limb-engine convolutions gather fp32 activations and gradients (gemm_x3.hip X3_F32A), bitwise the limb-gathering
   // form; DAMC_X3_F32A=0 (read per call) gathers limbs (CIFAR B=128 bench 51.1K -> 56.1K z-steps/s, B=16 per-rank
   // step 0.625 -> 0.478 ms; profiles/r04/bench_f32a_ab.txt, step_f32a_ab.txt)
   const char* fa = getenv("DAMC_X3_F32A");

@@ -23,7 +23,7 @@ SmallcGather smallc_gather_path(const damc_layer_t& L, int B);
 // carries them, and a limb-engine producer writes them) ...
 bool smallc_dgrad_reads_bits(const damc_layer_t& L);
 // ... the form the gradient leaves in -- fp32 in place of the activation, x3 limbs only, or fp32 for a limb-engine
-// dgrad that gathers fp32 (gemm.hip X3_F32A).  bits: sign bits carry the mask; limbs: the dgrad below reads through
+// dgrad that gathers fp32 (gemm_x3.hip X3_F32A).  bits: sign bits carry the mask; limbs: the dgrad below reads through
 // the limb engine; f32a: that dgrad gathers fp32
 enum SmallcGrad { SMALLC_GRAD_F32, SMALLC_GRAD_LIMBS, SMALLC_GRAD_F32A };
 SmallcGrad smallc_grad_form(const damc_layer_t& L, bool bits, bool limbs, bool f32a);

@@ -2,7 +2,7 @@
 // and the residual delta = (x_hat - x)/s^2 * (1 - x_hat^2), and its input gradient.  h is NHWC fp32, x / x_hat
 // NCHW.  Four generations of kernels, each the fallback of the next by shape (output layer: the
 // reachability table): generic, register-resident, two-stage projection + gather, proj16 / fused epilogue
-// (gemm.hip) with the limb-engine dgrad.  The choices are the functions declared in smallc.h, at the end of
+// (gemm_x3.hip) with the limb-engine dgrad.  The choices are the functions declared in smallc.h, at the end of
 // this file.  The layer's weight gradient is in wgrad.hip.
 #include <algorithm>
 #include <cstdlib>
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(256) void smallc_dgrad_k3_kernel(float* __restrict_
 // unit's 16 x 384 B of limbs leave through a per-wave LDS image as whole 16-B chunks.  Output lane l holds channels
 // 16 i + 4 (l >> 4) + r of pixel l & 15, so the LReLU' nibble of the sign bits applies directly.
 // F32O (round 4): the gradient leaves as fp32 NHWC (4 B per element: the next dgrad stages its A operand as fp32,
-// gemm.hip X3_F32A) through a per-wave image of 272-B pixel rows (8 rows of a ds_write_b128 group on 8 distinct
+// gemm_x3.hip X3_F32A) through a per-wave image of 272-B pixel rows (8 rows of a ds_write_b128 group on 8 distinct
 // 4-bank groups), 4 wave-instructions of 16-B stores per unit; the values are the limb form's before its split.
 // KT x KT taps at stride ST (round 4: also the k4 s2 p1 output layer of the 64x64 / 256x256 generators, whose K =
 // 16 NC = 48 runs as two 32-deep k steps per limb product, both in one accumulation chain; pixel y's window is
@@ -1244,7 +1244,7 @@ SmallcFwd smallc_fwd_path(const damc_layer_t& L, bool have_pbuf, bool by_shape) 
   // at most 2 column tiles (every known_taps layer has that few)
   if (!(have_pbuf && known_taps(L) && L.cin % 8 == 0 && smallc_ntile(L) <= 2 && L.w_bwd))
     return smallc_reg_ok(L) ? SMALLC_FWD_REG : SMALLC_FWD_GENERIC;
-  // proj16 (gemm.hip launch_proj_rows; the arithmetic of the fused ConvT epilogue) up to 256 channels
+  // proj16 (gemm_x3.hip launch_proj_rows; the arithmetic of the fused ConvT epilogue) up to 256 channels
   const char* p16 = by_shape ? nullptr : getenv("DAMC_SMALLC_PROJ16");
   if (L.cin <= 256 && L.cin % 16 == 0 && !(p16 && p16[0] == '0')) return SMALLC_FWD_PROJ16;
   // the round-3 kernels: LDS-staged when Cin is whole 64-channel chunks, else direct loads

@@ -2,7 +2,7 @@
 // (workspace/train_gen_recon.py:222-231: x_hat = G(z); sum((x_hat - x)^2).mean().backward()).
 //
 // The k4 s2 p1 and first-layer weight gradients are GEMMs over pixels and samples; they run on the limb
-// engine (gemm.hip, O_WGRAD) over PIXEL-MAJOR transposed operands written here: [channel][pixel][sample]
+// engine (gemm_x3.hip, O_WGRAD) over PIXEL-MAJOR transposed operands written here: [channel][pixel][sample]
 // with the sample index fastest, so a 32-deep K tile is 32 samples of one pixel and a filter tap is a
 // pixel shift of a whole K tile (no per-element masks, 16-B aligned limb loads).  The output layer
 // (Cout <= 4) has N = k*k*Cout <= 64 and reads one large activation once: a direct kernel with the
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void transpose_x3_kernel(const float* __restri
     if (c < C) {
       wg_bf16x8 h, m, l;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {  // RNE limb split, as the engine's own split (gemm.hip split3_octet)
+      for (int e = 0; e < 8; ++e) {  // RNE limb split, as the engine's own split (gemm_impl.h split3_octet)
         const float v = tile[cl][oct * 8 + e];
         const __bf16 b0 = (__bf16)v;
         const float r1 = sub_rn(v, (float)b0);

@@ -376,7 +376,7 @@ def x3_conv_negk(m_per_sample, N, K, zdim):
 
 
 def x3_ksplit(M, N, K, zdim, negk, bm=256, bn=128):
-    """csrc/gemm.hip x3_ksplit with its defaults: the sign blocks an under-filled limb-engine conv splits into."""
+    """csrc/gemm_x3.hip x3_ksplit with its defaults: the sign blocks an under-filled limb-engine conv splits into."""
     wgs = ((M + bm - 1) // bm) * ((N + bn - 1) // bn) * zdim
     if K % negk or K // negk < 2:
         return 1

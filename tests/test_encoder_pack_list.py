@@ -1,4 +1,4 @@
-"""CPU: the encoder's one-launch weight packing list (gemm.h PackConvList, gemm.hip pack_conv_x3_many_prep, the
+"""CPU: the encoder's one-launch weight packing list (gemm.h PackConvList, x3_pack.hip pack_conv_x3_many_prep, the
 device-side pack_conv_x3_block) restated on the host for every encoder the drivers build (diffusion_net.py:227-413 at
 nif=64, nemb=1024): the prepared grid is exactly the work list -- every (layer, output channel, channel chunk) is
 packed by exactly one workgroup, no workgroup falls outside the list, and a list prepared twice is refused (the

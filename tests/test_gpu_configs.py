@@ -260,7 +260,7 @@ def test_celebaHQ_b64_likelihood_gradient_vs_fp64(gpu_device):
     g64 = orc.likelihood_grad(L64, z0.cpu().double(), x.cpu().double(), 1.0)[0].numpy()
     # 7 layers, 5 of them k4 s2 p1 with K = 16 Cout up to 16384, then the first layer's 32768-term sum: a bias in
     # the GEMM's rounding survives that sum where noise cancels, so this is the test of the limb engine's blocked,
-    # sign-alternating accumulation (gemm.hip; without it the HIP median was 13x the fp32 reference's)
+    # sign-alternating accumulation (gemm_x3.hip; without it the HIP median was 13x the fp32 reference's)
     _check("celebaHQ B=64 likelihood gradient", g, g32, g64, 1e-7, per_row=True)
     xh = lv.generator_forward(z0, G).cpu().numpy()
     _check("celebaHQ B=64 G(z)", xh, orc.generator_sample(L32, z0.cpu()).numpy(),
@@ -309,7 +309,7 @@ def test_encoder_limb_engine_vs_fp32_engine_b128(gpu_device):
 
 @pytest.mark.parametrize("name,B", [("cifar10", 128), ("celeba64", 32), ("cifar10", 16)])
 def test_encoder_f32a_convs_are_bitwise(gpu_device, monkeypatch, name, B):
-    """The encoder's k4 s2 limb convs staging their input as fp32 (gemm.hip X3_F32A, the one-pass norms writing fp32
+    """The encoder's k4 s2 limb convs staging their input as fp32 (gemm_x3.hip X3_F32A, the one-pass norms writing fp32
     in place) against the limb inputs (DAMC_ENC_F32A=0), and the one-pass norms summing the convs' split-K slabs
     themselves (GemmArgs::ksplit_deferred) against the reduce kernel (DAMC_ENC_IN_SLABS=0): the in-register split is
     the producing epilogue's RNE split and the slab sum the reduce's order, so xemb is bitwise the same."""

@@ -197,7 +197,7 @@ def test_conv2d_x3_matches_fp64(gpu_device, monkeypatch, case):
     y = _conv_x3(gpu_device, case, xd, bd, w3)
     r32, r64 = U.conv_refs(case)
     U.check("conv2d_x3 %s" % U.case_id(case), _np(y), r32, r64, U.CONV_SLICES)
-    # the sign-block split-K sums its slabs in the unsplit launch's order: bitwise the same output (gemm.hip x3_ksplit)
+    # the sign-block split-K sums its slabs in the unsplit launch's order: bitwise the same output (gemm_x3.hip x3_ksplit)
     monkeypatch.setenv("DAMC_X3_KSPLIT", "0")
     y0 = _conv_x3(gpu_device, case, xd, bd, w3)
     assert torch.equal(y.view(torch.int32), y0.view(torch.int32)), "DAMC_X3_KSPLIT=0 changes the bits"

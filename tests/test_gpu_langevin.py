@@ -337,7 +337,7 @@ def test_g_update_backward_runs_on_the_forward_engine(gpu_device):
 
 @pytest.mark.parametrize("net,B", [("cifar10", 4), ("cifar10", 16), ("svhn", 64), ("celeba64", 32), ("celebaHQ", 8)])
 def test_split_k_is_bitwise_the_unsplit_kernel(lv, gpu_device, monkeypatch, net, B):
-    """Split-K of the limb-engine convs at small batch (gemm.hip x3_ksplit: one sign block per slice, summed in the
+    """Split-K of the limb-engine convs at small batch (gemm_x3.hip x3_ksplit: one sign block per slice, summed in the
     kernel's order and rounding) gives the same bits as the unsplit kernel: 3 posterior steps at full width with
     DAMC_X3_KSPLIT=0 vs the default -- F32A, register slabs, the reduce launch with the fused output-layer projection
     -- vs the two-kernel projection (DAMC_REDUCE_PROJ=0); and, at CIFAR, split-K on the limb-gathering path
@@ -420,7 +420,7 @@ def test_fused_posterior_update_is_bitwise(lv, gpu_device, monkeypatch, B):
 @pytest.mark.parametrize("name,B", [("cifar10", 16), ("cifar10", 128), ("svhn", 64), ("celeba64", 32)])
 def test_f32a_posterior_is_bitwise(lv, gpu_device, monkeypatch, name, B):
     """DAMC_X3_F32A=1: the limb-engine convolutions gather fp32 activations / gradients and split them into limbs in
-    registers (gemm.hip X3_F32A), the output layer's dgrad writes fp32: 2 noisy posterior steps bitwise equal to the
+    registers (gemm_x3.hip X3_F32A), the output layer's dgrad writes fp32: 2 noisy posterior steps bitwise equal to the
     limb-gathering path (B=16 runs split-K with register slabs, B=128 unsplit)."""
     from damc import synth
     from src import diffusion_net as dn
@@ -444,7 +444,7 @@ def test_f32a_posterior_is_bitwise(lv, gpu_device, monkeypatch, name, B):
 
 @pytest.mark.parametrize("B,f32a", [(16, "1"), (128, "1"), (16, "0"), (128, "0")])
 def test_fused_output_projection_is_bitwise(lv, gpu_device, monkeypatch, B, f32a):
-    """The last ConvT's epilogue runs the output layer's per-tap projection (gemm.hip GemmArgs::proj_out; B=16
+    """The last ConvT's epilogue runs the output layer's per-tap projection (gemm_x3.hip GemmArgs::proj_out; B=16
     splits K, so there the projection runs as proj_rows_kernel over the reduce's output): 2 noisy posterior steps
     bitwise equal to the separate projection kernel (DAMC_SMALLC_FUSE=0), which shares proj16's arithmetic and its
     128-channel chunks.  Both tiles: the F32A kernel (each 128-channel N tile projects its chunk) and the
@@ -464,7 +464,7 @@ def test_fused_output_projection_is_bitwise(lv, gpu_device, monkeypatch, B, f32a
 
 @pytest.mark.parametrize("B", [8, 16, 32, 48, 64, 128])
 def test_skinny_first_layer_is_bitwise(lv, gpu_device, monkeypatch, B):
-    """The first layer at per-rank batches (B <= 32): z . W on gemm.hip's x3_skinny_kernel and its input gradient's
+    """The first layer at per-rank batches (B <= 32): z . W on gemm_x3.hip's x3_skinny_kernel and its input gradient's
     split-K slabs on km_skinny_kernel (fragments straight into registers; up to B = 64, as 32-row workgroups): 2 noisy
     posterior steps bitwise equal to the tiled kernels (DAMC_X3_SKINNY=0, DAMC_KM_SKINNY=0), with the skinny kernel
     reading the weights as fp32 rows split in registers (round 5, default) and as the packed limbs

@@ -1,4 +1,4 @@
-"""GPU: the LDS limb image of the tap-shared limb GEMM (gemm.hip X3_TAPSHARE, round 9) -- a group's staged fp32 image is
+"""GPU: the LDS limb image of the tap-shared limb GEMM (gemm_x3.hip X3_TAPSHARE, round 9) -- a group's staged fp32 image is
 split into its bf16 limbs once, and the four taps read their MFMA A fragments from the limb image at displaced rows.
 
 * the per-op hooks damc_convT_fwd / damc_convT_dgrad (masked and unmasked) against fp64 conv_transpose2d / conv2d at the

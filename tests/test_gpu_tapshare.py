@@ -1,4 +1,4 @@
-"""GPU: the tap-shared A staging of the limb GEMM (gemm.hip X3_TAPSHARE) -- one fp32 input image per group of four K
+"""GPU: the tap-shared A staging of the limb GEMM (gemm_x3.hip X3_TAPSHARE) -- one fp32 input image per group of four K
 tiles (a ConvT phase's four taps, or the four taps of a parity class of its input gradient) instead of one per tap.
 
 * the per-op hooks damc_convT_fwd / damc_convT_dgrad against fp64 conv_transpose2d / conv2d at the project's ConvT

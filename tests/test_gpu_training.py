@@ -7,7 +7,7 @@ full norms, tests/golden/*_gtrain.npz) and (b) the oracle's explicit backward on
 
 Tolerance: rel-L2 <= 2e-5 per parameter tensor against the reference (fp32 results summed in a different
 order over up to B*H*W = 131K terms; the limb engine's products carry fp32's 24 significand bits,
-gemm.hip); at full width, accuracy-relative against fp64 (see the full-width test).
+gemm_x3.hip); at full width, accuracy-relative against fp64 (see the full-width test).
 """
 import numpy as np
 import pytest

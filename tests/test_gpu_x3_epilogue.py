@@ -1,4 +1,4 @@
-"""GPU: the tap-shared limb GEMM tile's own epilogue (gemm.hip X3_TAPSHARE, round 14) -- the fused projection on
+"""GPU: the tap-shared limb GEMM tile's own epilogue (gemm_x3.hip X3_TAPSHARE, round 14) -- the fused projection on
 preloaded weight fragments with the output pixel from a row table, row tables by shifts, one bias load per thread, and
 the read table built behind the first DMA.  None of it changes an output byte:
 

@@ -1,4 +1,4 @@
-"""GPU: the tap-shared K loop of the limb GEMM on the 4 (M) x 2 (N) wave grid (gemm.hip X3_TAPSHARE, round 11) -- what
+"""GPU: the tap-shared K loop of the limb GEMM on the 4 (M) x 2 (N) wave grid (gemm_x3.hip X3_TAPSHARE, round 11) -- what
 a wave grid newly gets wrong is a wave row or a wave column that lies partly or wholly outside the GEMM.
 
 * two noisy posterior steps at ngf = 32, the smallest width the tap-shared path accepts, default against per-tap staging

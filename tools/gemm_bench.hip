@@ -11,7 +11,11 @@
 #include <cstring>
 #include <vector>
 
+// the engines' file-local launch templates (launch_t, launch_km_t, launch_x3_t) and the operand packers
 #include "../diffusion-amortized-mcmc_amd/csrc/gemm.hip"
+#include "../diffusion-amortized-mcmc_amd/csrc/gemm_km.hip"
+#include "../diffusion-amortized-mcmc_amd/csrc/gemm_x3.hip"
+#include "../diffusion-amortized-mcmc_amd/csrc/x3_pack.hip"
 
 namespace damc_prof {
 bool enabled() { return false; }
