@@ -2342,6 +2342,24 @@ struct Stages {
   bool skinny;
 };
 
+// the shape predicates the stages and the dispatch branch on; damc_sweep_stages / damc_sweep_form report the same calls
+static bool stages_skinny(const damc_denoiser_t* d) {
+  bool skinny = (d->ntemb & 15) == 0 && (d->nxemb & 3) == 0;
+  for (int j = 0; j < (narrow_out2(d) ? 6 : 7); ++j) skinny = skinny && (d->blocks[j].dout & 15) == 0;
+  return skinny;
+}
+
+// blocks whose hyper GEMM runs on hyper_x3_kernel (bit j), by shape: the stage's one grouped launch takes blocks
+// 0 .. nb - 1 together, so every one of them has to fit it (K = dout in whole 32-deep tiles, at most HY_NTMAX of
+// them), or the stage runs on the fp32 engine whole
+static int hyper_limb_blocks(const damc_denoiser_t* d, int nb, const int* coloff) {
+  for (int j = 0; j < nb; ++j) {
+    const int dout = d->blocks[j].dout;
+    if (!(dout % 32 == 0 && dout <= HY_NTMAX * HY_KT && coloff[j] % 4 == 0)) return 0;
+  }
+  return (1 << nb) - 1;
+}
+
 static void stages_init(Stages& st, const damc_denoiser_t* d, int B, int n, void* wsp, hipStream_t s) {
   st.d = d;
   carve(d, B, n, reinterpret_cast<char*>(wsp), &st.w);
@@ -2355,8 +2373,7 @@ static void stages_init(Stages& st, const damc_denoiser_t* d, int B, int n, void
   }
   st.narrow = narrow_out2(d);
   st.nb = st.narrow ? 6 : 7;
-  st.skinny = (st.nt & 15) == 0 && (st.nx & 3) == 0;
-  for (int j = 0; j < st.nb; ++j) st.skinny = st.skinny && (d->blocks[j].dout & 15) == 0;
+  st.skinny = stages_skinny(d);
 }
 
 // ---- 1. pack the live weights
@@ -2566,7 +2583,7 @@ static int stage_hyper(const Stages& st, const float* cx, float* gh, long M) {
   // keeps the fp32-MFMA engine below
   const char* hye = getenv("DAMC_SWEEP_HYPER");
   bool hy_ok = !(hye && strcmp(hye, "fp32") == 0) && (S % 4 == 0) && ((uintptr_t)cx % 16 == 0) &&
-               ((uintptr_t)gh % 16 == 0);
+               ((uintptr_t)gh % 16 == 0) && hyper_limb_blocks(d, nb, coloff) != 0;
   HyperGroup hgp{};
   hgp.n = nb;
   {
@@ -2576,8 +2593,7 @@ static int stage_hyper(const Stages& st, const float* cx, float* gh, long M) {
   for (int j = 0; j < nb && hy_ok; ++j) {
     const damc_csq_block_t& bk = d->blocks[j];
     const int dout = bk.dout;
-    hy_ok = dout % 32 == 0 && dout <= HY_NTMAX * HY_KT && bk.wg && bk.wb && (uintptr_t)bk.wg % 16 == 0 &&
-            (uintptr_t)bk.wb % 16 == 0 && coloff[j] % 4 == 0;
+    hy_ok = bk.wg && bk.wb && (uintptr_t)bk.wg % 16 == 0 && (uintptr_t)bk.wb % 16 == 0;
     HyperBlock& h = hgp.b[j];
     h.a = cx + coloff[j];
     h.lda = S;
@@ -2674,6 +2690,23 @@ static double rows_flops(const damc_denoiser_t* d, double rows, int n) {
   return fl * n;
 }
 
+// ---- the dispatch's two decisions (damc_sweep_form asks the same two)
+// the row-resident form: a narrow out2 has no other, DAMC_SWEEP_ROWS=1 asks for it
+static bool sweep_rows(const damc_denoiser_t* d) { return narrow_out2(d) || rows_forced(); }
+
+// the team launch (its arguments in *ta, *tP, *tsm) or, false, the launch chain.  w may be carved from a null base
+// (damc_sweep_form): team_plan only copies its pointers.
+static bool sweep_team(const damc_denoiser_t* d, const SweepWs& w, int B, int n, bool capturing, int dev, TsArgs* ta,
+                       int* tP, size_t* tsm) {
+  // inside a caller's capture the team launch is recorded like any kernel (DAMC_SWEEP_CAPTURE_TEAM=0, read per
+  // call: the launch chain instead).  What the team kernel needs zeroed or filled, the setup kernel writes: a kernel
+  // is ordered before it in a replay as in the stream (a memset node was not: DESIGN.md §1).
+  const char* tic = getenv("DAMC_SWEEP_CAPTURE_TEAM");
+  const bool team_in_capture = !(tic && tic[0] == '0');
+  return (!capturing || team_in_capture) && team_enabled() && dev < 64 && team_healthy(dev) &&
+         team_plan(d, w, B, n, ta, tP, tsm) == 0;
+}
+
 // step_offset: Philox step index of the first noisy step (a single-step call continues a sweep's noise stream)
 static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float* zt, int B, int n,
                               const float* temb_in, const float* coef, int with_noise, const float* noise,
@@ -2690,7 +2723,7 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   stages_init(st, d, B, n, wsp, s);
   const SweepWs& w = st.w;
   const int S = st.S;
-  const bool rows = st.narrow || rows_forced();
+  const bool rows = sweep_rows(d);
   if (rows && !rows_fit(d)) return DAMC_ERR_UNSUPPORTED;
 
   // ---- 1-3: the weights, then everything that does not depend on zt: ctx c for every (step, row) from the time MLP
@@ -2729,13 +2762,7 @@ static int reverse_sweep_impl(const damc_denoiser_t* d, const float* xemb, float
   const bool capturing = cap != hipStreamCaptureStatusNone;
   int dev = 0;
   DAMC_CHECK(hipGetDevice(&dev));
-  // inside a caller's capture the team launch is recorded like any kernel (DAMC_SWEEP_CAPTURE_TEAM=0, read per
-  // call: the launch chain instead).  What the team kernel needs zeroed or filled, the setup kernel writes: a kernel
-  // is ordered before it in a replay as in the stream (a memset node was not: DESIGN.md §1).
-  const char* tic = getenv("DAMC_SWEEP_CAPTURE_TEAM");
-  const bool team_in_capture = !(tic && tic[0] == '0');
-  const bool team = (!capturing || team_in_capture) && team_enabled() && dev < 64 && team_healthy(dev) &&
-                    team_plan(d, w, B, n, &ta, &tP, &tsm) == 0;
+  const bool team = sweep_team(d, w, B, n, capturing, dev, &ta, &tP, &tsm);
   int* health = team ? team_health_word(dev, capturing) : nullptr;
   // the data-driven hand-off's sentinels: every ring slot of the sweep (TS_SENT)
   const long nzero = team ? 1 : 0, ns1 = team ? (long)n * B * S / 4 : 0, ns2 = team ? (long)n * nzb / 4 : 0;
@@ -2803,6 +2830,38 @@ extern "C" int damc_denoise_step(const damc_denoiser_t* d, const float* xemb, fl
                             eps ? 1 : 0, wsp, wsb, stream, noise_step, false);
 }
 
+// what the per-call stages of this denoiser run on, by shape alone (pointers taken as 16-byte aligned, no environment
+// switch read): the predicates stages_init and stage_hyper branch on
+extern "C" int damc_sweep_stages(const damc_denoiser_t* d) {
+  const int rc = validate(d);
+  if (rc) return -rc;
+  const bool narrow = narrow_out2(d);
+  int coloff[7];
+  for (int j = 0, o = 0; j < 7; ++j) {
+    coloff[j] = o;
+    o += lay_dout(d->blocks[j].dout);
+  }
+  return (stages_skinny(d) ? 1 : 0) | (narrow ? 2 : 0) | (rows_fit(d) ? 4 : 0) |
+         (hyper_limb_blocks(d, narrow ? 6 : 7, coloff) << 8);
+}
+
+// the form reverse_sweep_impl would take now for (d, batch, n_steps) on the current device, outside a capture:
+// 0 none (the sweep would refuse), 1 row-resident, 2 team on the generic kernel, 3 team on sweep_fast_kernel,
+// 4 launch chain.  The environment switches are read as the sweep reads them; nothing is launched.
+extern "C" int damc_sweep_form(const damc_denoiser_t* d, int B, int n) {
+  if (validate(d) || B <= 0 || n <= 0) return 0;
+  if (sweep_rows(d)) return rows_fit(d) ? 1 : 0;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  SweepWs w;
+  carve(d, B, n, nullptr, &w);
+  TsArgs ta;
+  int tP = 0;
+  size_t tsm = 0;
+  if (!sweep_team(d, w, B, n, false, dev, &ta, &tP, &tsm)) return 4;
+  return ta.fast ? 3 : 2;
+}
+
 // ------------------------------------------------------------------------------------- the guided sweep
 // Classifier-free guidance (_netQ_U.forward with cond_w > 0, workspace/src/diffusion_net.py:595-620) as one sweep: the
 // reference evaluates the denoiser twice per step, on the encoder's xemb and on a fresh prior_emb(randn), and steps on
@@ -2829,8 +2888,7 @@ size_t carve_guided(const damc_denoiser_t* d, int B, int n, char* base, GuidedWs
     return p;
   };
   const long S = sum_dout(d), M = (long)n * B;
-  bool skinny = (d->ntemb & 15) == 0 && (d->nxemb & 3) == 0;
-  for (int j = 0; j < 7; ++j) skinny = skinny && (d->blocks[j].dout & 15) == 0;
+  const bool skinny = stages_skinny(d);  // (guided_ok: never narrow, all 7 blocks)
   GuidedWs t;
   t.px_u = take(M * S);
   t.cx_u = take(M * S);

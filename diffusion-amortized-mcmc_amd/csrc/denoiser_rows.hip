@@ -272,7 +272,10 @@ int rows_layout(int nz, int w, int kp0, RowsBlock* b) {
     b[j].src = src[j];
     b[j].dst = dst[j];
   }
-  return o0 + (w + 63) / 64 * 64 + 4;  // in1 reads o0 over its padded K
+  // in1 reads o0 over its padded K, and out2 reads [P | o0] over its own: at 32 < w % 64 < 64 (48, 112, 176, 240 of
+  // the multiples of 16) pad64(2 w) reaches past o0's pad64(w), and launch_rows refuses an image a block reads beyond
+  const int p64 = (w + 63) / 64 * 64, p2 = (2 * w + 63) / 64 * 64;
+  return (o0 + p64 > P + p2 ? o0 + p64 : P + p2) + 4;
 }
 
 namespace {

@@ -254,6 +254,8 @@ _SIGS = {
     "damc_pack_conv2d_x3": (_I, [_P, _I, _I, _I, _P, _P]),
     "damc_sweep_workspace_bytes": (_SZ, [ctypes.POINTER(Denoiser), _I, _I]),
     "damc_sweep_team_failures": (ctypes.c_long, [_I]),
+    "damc_sweep_stages": (_I, [ctypes.POINTER(Denoiser)]),
+    "damc_sweep_form": (_I, [ctypes.POINTER(Denoiser), _I, _I]),
     "damc_reverse_sweep": (_I, [ctypes.POINTER(Denoiser), _P, _P, _I, _I, _P, _P, _I, _P, _U64, _U64, _P, _I, _P,
                                 _SZ, _P]),
     "damc_q_reverse_sweep": (_I, [ctypes.POINTER(Denoiser), _P, _P, _I, _I, _P, _P, _I, _P, _U64, _U64, _P, _I, _P,

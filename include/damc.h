@@ -495,12 +495,21 @@ size_t damc_sweep_workspace_bytes(const damc_denoiser_t* d, int batch, int n_ste
  * x Wl^T / x Ws^T products plus the reverse-step update — then runs as ONE team launch (weights LDS-resident,
  * data-driven hand-offs between the workgroups of a team; at the reference's widths, nf = 4 with nz 128 or 100, a
  * kernel with those shapes compiled in, DAMC_SWEEP_FAST=0 the generic one, bitwise the same); DAMC_SWEEP_TEAM=0
- * runs it as 7 launches per step replayed from a HIP graph cached per (workspace, shapes, schedule).
+ * runs it as 7 launches per step replayed from a HIP graph cached per (workspace, shapes, schedule).  The launch chain
+ * is also what a sweep takes by itself when a team's share of the weights does not fit a workgroup's LDS (in0's dout
+ * of 160 and more on a 256-CU device), when the device's CUs do not split into 8 groups, and after a rescue (below);
+ * damc_sweep_form tells which.  Accepted shapes: nz even, 4 <= nz <= 128 for these forms; in0's dout w % 4 == 0 with
+ * the block widths (din 2nz w 2w 2w 4w 4w 2w, dout w 2w 2w 2w 2w w nz); any ntemb, nxemb >= 1.  The per-call stages
+ * run on the skinny GEMM only when ntemb % 16 == 0, nxemb % 4 == 0 and every dout, nz included, is a multiple of 16
+ * (nz = 100 is not), and the hyper GEMMs on the limb product only when every dout, nz included, is a multiple of 32
+ * and at most 512 (damc_sweep_stages); otherwise on the fp32 GEMM.
  * A denoiser whose nz is no multiple of 4 (the toy's _netQ_U_toy, workspace/toy_example/src/diffusion_net.py:141-239,
  * nz = 2; any even nz <= 128) runs the chain in its row-resident form instead: one workgroup per 16 rows runs all
  * steps and blocks for them with the activations in LDS and nothing handed between workgroups (denoiser_rows.hip);
- * DAMC_SWEEP_ROWS=1 (read per call) takes that form for every shape.  Such a denoiser needs ntemb % 16 == 0,
- * nxemb % 4 == 0 and a width (in0's dout) that is a multiple of 16 (DAMC_ERR_UNSUPPORTED otherwise).
+ * DAMC_SWEEP_ROWS=1 (read per call) takes that form for every shape whose 16-row LDS image fits (16 x (kpad(2 nz) +
+ * 8 w + max(w + pad64(w), pad64(2 w)) + 4) floats within 156 KB; otherwise DAMC_ERR_UNSUPPORTED and a workspace size
+ * of 0 while the switch is set).  A denoiser with nz % 4 != 0 needs ntemb % 16 == 0, nxemb % 4 == 0, a width (in0's
+ * dout) that is a multiple of 16 and an image that fits: w <= 224 at nz = 10 (DAMC_ERR_UNSUPPORTED otherwise).
  *   eps = p(zt, l_t, xemb); pred = c0 * (zt - eps * c1); zt <- last ? pred : c2*zt + c3*pred (+ c4*xi)
  * temb_in (n_steps, ntemb): SinusoidalPosEmb of the step's logsnr input (host, fp32, as the reference);
  * coef (n_steps, 6), a HOST pointer: {sqrt(1+e^-lt), rsqrt(1+e^lt), r*alpha_st, (1-r)*alpha_s, std,
@@ -529,6 +538,23 @@ int damc_q_reverse_sweep(const damc_denoiser_t* d, const float* xemb, float* zt,
  * damc_sweep_team_failures: how many such rescued launches this process has seen on a device (a rescue still in
  * flight is counted once it completes). */
 long damc_sweep_team_failures(int device);
+/* Two host queries of the sweep's dispatch, computed by the predicates the sweep itself branches on; neither launches
+ * anything.
+ * damc_sweep_stages: what the per-call stages run on, by shape alone (pointers taken as 16-byte aligned, no environment
+ * switch read).  A refused denoiser gives minus its error code (-DAMC_ERR_ARG, -DAMC_ERR_UNSUPPORTED); otherwise a mask:
+ *   bit 0      the time MLP and ctx Linears run on the skinny GEMM (ntemb % 16 == 0, nxemb % 4 == 0 and every block's
+ *              dout % 16 == 0, out2 aside when nz % 4 != 0); clear: on the fp32 GEMM over transposed copies
+ *   bit 1      nz % 4 != 0: out2's columns of the stages come from the narrow kernels, the chain is row-resident
+ *   bit 2      the row-resident form's LDS image of 16 rows fits (DAMC_SWEEP_ROWS=1 is available)
+ *   bits 8-14  block j's gate / hyper-bias GEMM runs on the limb product.  The blocks go in one grouped launch, so
+ *              these are all set (bits 8-13 when bit 1 is set) or none: every block needs dout % 32 == 0 and
+ *              dout <= 512, or the whole stage runs on the fp32 engine.
+ * damc_sweep_form: the form damc_reverse_sweep would take now for (batch, n_steps), on the current device, outside a
+ * stream capture, with DAMC_SWEEP_ROWS / _TEAM / _FAST read as the sweep reads them: 0 none (the sweep refuses),
+ * 1 row-resident, 2 team launch on the generic kernel, 3 team launch on the shape-specialised kernel, 4 launch chain
+ * (the team disabled, this device flagged after a rescue, or the weights too wide for a team's LDS). */
+int damc_sweep_stages(const damc_denoiser_t* d);
+int damc_sweep_form(const damc_denoiser_t* d, int batch, int n_steps);
 /* per-op hook (SURVEY.md §8b damc_denoise_step): ONE reverse step = damc_reverse_sweep with n_steps = 1 on the
  * step's temb_row (ntemb) and coef_row (6, HOST); noise (B, nz) injected or NULL for Philox at step index
  * noise_step (the k-th noisy step of a sweep uses k); eps (B, nz) receives the denoiser output or NULL.
