@@ -1,4 +1,4 @@
-// denoiser_rows.h — the row-resident reverse sweep (denoiser_rows.hip) as denoiser.hip calls it.
+// denoiser_rows.h — the row-resident reverse sweep (denoiser_rows.hip) as denoiser.hip and sweep_stages.hip call it.
 #pragma once
 #include "common.h"
 

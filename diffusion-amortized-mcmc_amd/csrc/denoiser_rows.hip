@@ -6,7 +6,7 @@
 // latent row, below), and nothing is handed between workgroups: no flags, no sentinels, no wait, no rescue path.
 // The weights are read from the workspace in the layout pack_denoiser_kernel writes for the launch chain
 // ([ntn][16][kp], rows 0-7 Wl, 8-15 Ws of 8 output columns) as f32x4 B fragments of v_mfma_f32_16x16x4_f32, through
-// the k-permutation of denoiser.hip (MFMA step s of k-group g reads k = 16 g + 4 (lane >> 4) + s on both operands);
+// the k-permutation of sweep_chain.hip (MFMA step s of k-group g reads k = 16 g + 4 (lane >> 4) + s on both operands);
 // they stream from L2 once per step and workgroup, double-buffered 64 k ahead of the MFMAs.  Wave w takes the column
 // tiles w, w + 4, ... two at a time over the whole K, each tile on two accumulator chains (even and odd k-groups):
 // four independent chains per wave where a block has eight tiles or more, against the instruction's 40-cycle

@@ -286,7 +286,7 @@ __global__ void dz_kernel(const float* __restrict__ g, const float* __restrict__
 // ------------------------------------------------------------------ nz % 4 != 0 (the toy amortizer, nz = 2)
 // The GEMM engines take float4 rows of A (K % 4 == 0, lda % 4 == 0).  With nz even and no multiple of 4, out2 is laid
 // out with dout padded to dp = the next multiple of 4 (zero weight rows / columns and zero biases in the packed
-// workspace, as the sweep's lay_dout does, denoiser.hip), so every stacked width and leading dimension is a multiple
+// workspace, as the sweep's lay_dout does, sweep_impl.h), so every stacked width and leading dimension is a multiple
 // of 4 and its padded columns evaluate to exact zeros; the K = nz and K = nz / 2 products around the Fourier embedding
 // are the kernels below.  None of this runs for nz % 4 == 0.
 

@@ -5,7 +5,7 @@
 // One 256-thread workgroup owns 16 rows; the activations ping-pong between two LDS images, and the weights are read
 // where PyTorch keeps them ((out, in), k contiguous), so there is no packing and no workspace.  A layer whose K is a
 // multiple of 16 (and whose weight is 16-B aligned) runs on v_mfma_f32_16x16x4_f32: wave w takes the 16-column tiles
-// w, w + 4, ..., each on two accumulator chains (even / odd k-groups), with the k-permutation of denoiser.hip (MFMA
+// w, w + 4, ..., each on two accumulator chains (even / odd k-groups), with the k-permutation of sweep_chain.hip (MFMA
 // step s of k-group g reads k = 16 g + 4 (lane >> 4) + s on both operands, one f32x4 load each).  Any other K (the
 // toy's K = 2 input layers) is plain FMAs, one (row, column) per thread.
 //

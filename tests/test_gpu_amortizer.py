@@ -232,7 +232,7 @@ def test_team_sweep_is_deterministic(am, gpu_device):
 
 @pytest.mark.parametrize("B", [37, 128])
 def test_limb_hyper_gemms_vs_fp32_engine(am, gpu_device, monkeypatch, B):
-    """The hyper GEMMs on the limb product (denoiser.hip hyper_x3_kernel, round 5: the PyTorch Wg / Wb rows read as
+    """The hyper GEMMs on the limb product (sweep_stages.hip hyper_x3_kernel, round 5: the PyTorch Wg / Wb rows read as
     fp32 and split in the kernel) against the fp32-MFMA grouped launch (DAMC_SWEEP_HYPER=fp32): the first step's eps
     agrees to rel-L2 1e-5, and a 10-step sweep's end point is as close to the fp64 oracle (same injected noise): within
     3x the fp32 engine's distance (+1e-6).  B=37 leaves a partial 128-row tile in every block."""
