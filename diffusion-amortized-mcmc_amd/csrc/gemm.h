@@ -129,7 +129,7 @@ struct GemmArgs {
   // in_part[((b * N + n) * in_S + strip) * 3] (in_stats_kernel's layout, in_merge_kernel reads it), computed by
   // strip256_stats from the stored values; in_hw = output rows per sample (a multiple of 256), in_S = in_hw / 256.
   // in_done (host): the caller sets it to 1; a launcher that cannot write the statistics (a split-K or narrow launch)
-  // clears it, and the caller then runs encoder.hip's in_strip_stats_kernel (the same arithmetic) over C
+  // clears it, and the caller then runs enc_norm.hip's in_strip_stats_kernel (the same arithmetic) over C
   float* in_part = nullptr;
   int in_hw = 0, in_S = 0;
   int* in_done = nullptr;
@@ -139,7 +139,7 @@ struct GemmArgs {
 // threads: thread t takes channel t & 127 over rows 64 (t >> 7) .. + 63 in two passes (the sum, mean = sum / 64, then
 // the centred squares), and threads t < 128 merge the four quarters in order (Chan's pairwise update, in_stats_kernel's
 // wmerge at equal counts).  Fixed partition and order, every operation non-contractable, so the same values give the
-// same statistics in the conv's epilogue (gemm_x3_kernel, LDS tile) and in the stand-alone kernel (encoder.hip
+// same statistics in the conv's epilogue (gemm_x3_kernel, LDS tile) and in the stand-alone kernel (enc_norm.hip
 // in_strip_stats_kernel, global rows): the statistics, and so the normalised activation, do not depend on whether the
 // conv ran split, nor on the batch.  y: row r, channel c at y[r * ld + c] (LDS or global); live: c < the channel count;
 // red: 1024 floats of LDS; {n, mean, m2} returned in threads t < 128 (after the one barrier inside)
@@ -365,7 +365,7 @@ __device__ __forceinline__ void pack_conv_x3_block(const PackConvList& l, int bl
   }
 }
 
-// the encoder's dense head (encoder.hip enc_head_x3_kernel): out[M][N] = A . W^T + bias on the limb product, A [M][K]
+// the encoder's dense head (enc_head.hip enc_head_x3_kernel): out[M][N] = A . W^T + bias on the limb product, A [M][K]
 // and W [N][K] fp32 (a PyTorch Conv2d weight covering its whole input, with A the samples' CHW rows); N % 64 == 0,
 // K % 512 == 0, 16-B aligned A / W / slab / out; slab: K / 512 * M * N floats of scratch
 int launch_dense_head_x3(const float* a, const float* w, const float* bias, int M, int N, int K, float* slab,

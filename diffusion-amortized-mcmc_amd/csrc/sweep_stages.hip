@@ -212,7 +212,7 @@ __global__ void transpose_kernel(const float* in, int rows, int cols, float* out
 // over all n * B (step, row) pairs, K = dout <= 512: one limb-engine sign block, so no sign alternation.  The weights
 // are read as the PyTorch Linear rows themselves ([dout][dout], k contiguous; row n < dout of the [2 dout][dout] operand
 // is Wg's, the rest Wb's) and split into limbs on their way into LDS, with c's rows; one workgroup = 128 rows x 64
-// columns, 8 waves of 32 x 32, the limb engine's six-MFMA product (encoder.hip enc_head_x3_kernel has the same tile).
+// columns, 8 waves of 32 x 32, the limb engine's six-MFMA product (enc_head.hip enc_head_x3_kernel has the same tile).
 // The 7 blocks in one launch (tile table); the epilogue adds bg and applies the gate's sigmoid as gemm.hip's EPI_GATE.
 typedef __bf16 hy8 __attribute__((ext_vector_type(8)));
 typedef __bf16 hy4 __attribute__((ext_vector_type(4)));
@@ -231,7 +231,7 @@ struct HyperGroup {
   int exact_sig;  // 1: the gate's sigmoid as 1 / (1 + expf(-v)) with IEEE division (DAMC_SWEEP_HYPER_SIGMOID=exact)
 };
 
-__device__ __forceinline__ int hy_slot(int row, int q) {  // (encoder.hip hd_slot: conflict-free fragment reads)
+__device__ __forceinline__ int hy_slot(int row, int q) {  // (enc_head.hip hd_slot: conflict-free fragment reads)
   return row * 4 + (q ^ ((0x1320 >> (4 * ((row >> 2) & 3))) & 3));
 }
 template <int N>

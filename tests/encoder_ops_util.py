@@ -332,3 +332,165 @@ def assert_guards_intact():
         back = int((buf[lead + words:] != GUARD_WORD).sum().item())
         assert front == 0 and back == 0, ("guarded buffer %d (%d payload words): %d words overwritten in front, "
                                           "%d behind" % (i, words, front, back))
+
+
+# ------------------------------------------------------------------------------------------------ the whole forward
+# Shared by tests/test_encoder_forms_cases_cpu.py and tests/test_gpu_encoder_forms.py: the cases that run
+# damc_q_encoder_fwd on Encoder_* modules under every switch setting that changes which kernel runs, and the dispatch
+# predicates of csrc/encoder.hip (enc_shapes, damc_q_encoder_fwd), csrc/enc_first.hip (launch_first_layer) and
+# csrc/enc_head.hip (launch_dense_head_x3) restated in Python.
+FWD_B, FWD_NEMB = 2, 128
+
+# (Encoder_* name, image side, nc, nif, {DAMC_ENC_<switch>: value}, engine)
+FWD_CASES = [
+    ("cifar10", 32, 3, 64, {}, "limb"),                                                 # conv3_in_fused<3>
+    ("cifar10", 32, 3, 64, {"FIRST_ONEPASS": "0"}, "limb"),                             # conv3_mfma<3, 4, *>
+    ("cifar10", 32, 3, 64, {"FIRST_ONEPASS": "0", "FIRST_MFMA": "0"}, "limb"),          # conv3_stats<3, 4>, apply<3, 1>
+    ("cifar10", 32, 3, 64, {"FIRST_ONEPASS": "0", "FIRST_MFMA": "0", "FIRST_PX": "1"}, "limb"),  # conv3_stats<3, 1>
+    ("cifar10", 32, 3, 64, {"F32A": "0"}, "limb"),                                      # one-pass kernels' limb stores
+    ("cifar10", 32, 3, 64, {"IN_ONEPASS": "0"}, "limb"),                                # in_strip_stats, in_stats
+    ("cifar10", 32, 3, 64, {"IN_ONEPASS": "0", "IN_STRIP": "0"}, "limb"),               # in_stats at hw = 256 (S = 4)
+    ("cifar10", 32, 3, 64, {"IN_ONEPASS": "0", "F32A": "0"}, "limb"),                   # in_apply_x3 throughout
+    ("cifar10", 32, 3, 64, {"IN_ONEPASS": "0", "IN_STRIP": "0", "F32A": "0"}, "limb"),
+    ("cifar10", 32, 3, 64, {"HEAD": "0"}, "limb"),                                      # the last conv on the limb GEMM
+    ("cifar10", 32, 3, 64, {"HEAD": "1"}, "limb"),
+    ("cifar10", 32, 3, 64, {"HEAD_PD": "1"}, "limb"),                                   # enc_head_x3<1>
+    ("cifar10", 32, 3, 64, {}, "fp32"),                                                 # in_stats_pivot, in_apply
+    ("cifar10", 32, 4, 64, {}, "limb"),                                                 # conv3_in_fused<4>
+    ("cifar10", 32, 4, 64, {"FIRST_ONEPASS": "0"}, "limb"),                             # conv3_stats<4, 4>: no MFMA
+    ("cifar10", 32, 4, 64, {"FIRST_ONEPASS": "0", "FIRST_PX": "1"}, "limb"),            # conv3_stats<4, 1>
+    ("mnist", 28, 1, 64, {}, "limb"),                                                   # conv3_in_fused<1>, 3 x 3 head
+    ("mnist", 28, 1, 64, {"FIRST_ONEPASS": "0"}, "limb"),                               # conv3_stats<1, 4>: W % 16 != 0
+    ("mnist", 28, 1, 64, {"FIRST_ONEPASS": "0", "FIRST_PX": "1"}, "limb"),              # conv3_stats<1, 1>
+    ("celeba64", 64, 3, 64, {}, "limb"),                   # conv3_mfma<3, 4, *>, the strip norm at 1024 pixels
+    ("celeba64", 64, 3, 64, {"FIRST_MFMA": "0"}, "limb"),  # conv3_stats<3, 4> over 8 strips
+    ("celeba64", 64, 3, 64, {"IN_STRIP": "0"}, "limb"),    # in_stats at 1024 pixels (S = 16)
+    ("celeba64", 64, 3, 64, {"IN_ONEPASS": "0"}, "limb"),
+    ("celeba64", 64, 1, 64, {}, "limb"),                   # conv3_mfma<1, 4, *>
+    ("celeba64", 64, 3, 128, {}, "limb"),                  # conv3_mfma<3, 8, *>
+    ("celeba64", 64, 1, 128, {}, "limb"),                  # conv3_mfma<1, 8, *>
+]
+
+# the kernel instantiations of csrc/enc_norm.hip, csrc/enc_first.hip and csrc/enc_head.hip
+FWD_KERNELS = (
+    ["in_stats_kernel", "in_stats_pivot_kernel", "in_apply_kernel", "in_merge_kernel", "in_strip_stats_kernel",
+     "in_apply_f32_kernel", "in_apply_x3_kernel", "in_fused_x3_kernel<1>", "in_fused_x3_kernel<2>",
+     "in_fused_x3_kernel<4>", "in_apply_train_kernel", "in_bwd_sums_kernel", "in_bwd_apply_kernel"]
+    + ["conv3_in_fused_kernel<%d>" % c for c in (1, 3, 4)]
+    + ["conv3_stats_kernel<%d, %d>" % (c, p) for c in (1, 3, 4) for p in (1, 4)]
+    + ["conv3_apply_x3_kernel<%d, 1>" % c for c in (1, 3, 4)]
+    + ["conv3_mfma_kernel<%d, %d, %s>" % (c, t, s) for c in (1, 3) for t in (4, 8) for s in ("true", "false")]
+    + ["enc_head_x3_kernel<1>", "enc_head_x3_kernel<4>", "enc_head_reduce_kernel"])
+
+_ENC_TOPOLOGY = {  # src/diffusion_net.py: (hidden channel multipliers of nif, the last conv's kernel)
+    "cifar10": ((1, 2, 4, 8), 4), "celeba64": ((1, 2, 4, 8, 8), 4), "celebaHQ": ((1, 2, 4, 4, 8, 8, 8), 4),
+    "mnist": ((1, 2, 4, 8), 3)}
+
+
+def fwd_case_id(case):
+    name, hw, nc, nif, sw, engine = case
+    tag = "-".join("%s=%s" % kv for kv in sorted(sw.items())) or "default"
+    return "%s-%d-nc%d-nif%d-%s-%s" % (name, hw, nc, nif, engine, tag)
+
+
+def enc_layers(name, nc, nif, nemb=FWD_NEMB):
+    """[(cin, cout, k, stride, pad, has_norm)] of Encoder_<name>(nc, nemb, nif)."""
+    mults, k_last = _ENC_TOPOLOGY[name]
+    out, cin = [], nc
+    for i, m in enumerate(mults):
+        out.append((cin, nif * m) + ((3, 1, 1) if i == 0 else (4, 2, 1)) + (True,))
+        cin = nif * m
+    return out + [(cin, nemb, k_last, 1, 0, False)]
+
+
+def module_layers(enc):
+    """The same list read from an Encoder_* module."""
+    import torch
+
+    mods, out = list(enc.net), []
+    for i, m in enumerate(mods):
+        if isinstance(m, torch.nn.Conv2d):
+            norm = i + 1 < len(mods) and isinstance(mods[i + 1], torch.nn.InstanceNorm2d)
+            out.append((m.in_channels, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], norm))
+    return out
+
+
+def x3_ksplit(M, N, K, bm=256, bn=128, negk=512):
+    """csrc/gemm_x3.hip x3_ksplit's default rule (zdim = 1): the slices a limb conv's K is split into."""
+    wgs = ((M + bm - 1) // bm) * ((N + bn - 1) // bn)
+    if K % negk or K // negk < 2:
+        return 1
+    ks = K // negk
+    return ks if (wgs < 128 or (wgs < 256 and ks <= 16)) else 1
+
+
+def forward_kernels(layers, H, W, B, sw=None, engine="limb", slope=0.2):
+    """The kernel instantiations of enc_norm.hip, enc_first.hip and enc_head.hip that one damc_q_encoder_fwd call
+    launches, in launch order, for the layer list of enc_layers / module_layers as damc.amortizer.EncoderPlan describes
+    it (limb layers hand over their PyTorch weight, 16-byte aligned; xemb 16-byte aligned).  sw: DAMC_ENC_<key> values.
+    The convolutions, the weight packing and the limb splits (gemm*.hip, x3_pack.hip) are not listed."""
+    sw = sw or {}
+    off = lambda key: sw.get(key) == "0"  # noqa: E731
+    n = len(layers)
+    kmajor = lambda c: c > 0 and c % 32 == 0  # noqa: E731
+    limb = [engine == "limb" and kmajor(cin) and cout % 8 == 0 and k * k <= 32 for cin, cout, k, s, p, nm in layers]
+    h, w = [H], [W]
+    for cin, cout, k, s, p, nm in layers:
+        h.append((h[-1] + 2 * p - k) // s + 1)
+        w.append((w[-1] + 2 * p - k) // s + 1)
+    assert h[n] == 1 and w[n] == 1
+    cin0, C0, k0, s0, p0, nm0 = layers[0]
+    first_fused = (n > 1 and limb[1] and (k0, s0, p0) == (3, 1, 1) and cin0 in (1, 3, 4) and C0 % 64 == 0 and
+                   C0 <= 512 and nm0 and not kmajor(cin0) and W <= 1024)
+    nl = n - 1
+    cinh, couth, kh, sh_, ph, _ = layers[nl]
+    head_geom = (nl >= 2 and limb[nl] and sh_ == 1 and ph == 0 and h[nl] == kh and w[nl] == kh and couth % 64 == 0 and
+                 (cinh * kh * kh) % 512 == 0 and layers[nl - 1][5] and layers[nl - 1][1] % 32 == 0)
+    head = head_geom and not off("HEAD") and not off("IN_ONEPASS")
+
+    def f32a_layer(i):
+        return not off("F32A") and i < n and limb[i] and layers[i][2:5] == (4, 2, 1)
+
+    out, i0 = [], 0
+    if first_fused:
+        want = max(1, min(64, H * W // 512))
+        R = max((H + want - 1) // want, (128 + W - 1) // W)
+        assert ((R + 2) * (W + 2) * cin0 + 9 * cin0 * C0 + C0) * 4 <= 65536
+        sm1 = ((H + 2) * (W + 2) * cin0 + 9 * cin0 * 16 + 8 * 8 + 32) * 4
+        one = not off("FIRST_ONEPASS") and H * W <= 1024 and W % 4 == 0 and C0 % 16 == 0 and sm1 <= 65536
+        smw = 3 * (R + 2) * (W + 2) * cin0 * 2
+        mf = (not one and not off("FIRST_MFMA") and cin0 in (1, 3) and C0 in (64, 128) and W % 16 == 0 and
+              smw <= 49152 and 0.0 <= slope <= 1.0)
+        px = 4 if (W % 4 == 0 and sw.get("FIRST_PX") != "1") else 1
+        if one:
+            out.append("conv3_in_fused_kernel<%d>" % cin0)
+        elif mf:
+            out += ["conv3_mfma_kernel<%d, %d, true>" % (cin0, C0 // 16), "in_merge_kernel",
+                    "conv3_mfma_kernel<%d, %d, false>" % (cin0, C0 // 16)]
+        else:
+            out += ["conv3_stats_kernel<%d, %d>" % (cin0, px), "in_merge_kernel",
+                    "conv3_apply_x3_kernel<%d, 1>" % cin0]
+        i0 = 1
+    for i in range(i0, n):
+        cin, cout, k, s, p, nm = layers[i]
+        hw = h[i + 1] * w[i + 1]
+        if head and i == n - 1:
+            out += ["enc_head_x3_kernel<%d>" % (1 if sw.get("HEAD_PD") == "1" else 4), "enc_head_reduce_kernel"]
+            continue
+        nxt = i + 1 < n and limb[i + 1]
+        in1 = nm and nxt and cout % 32 == 0 and hw <= 256 and not off("IN_ONEPASS")
+        strip = (nm and not in1 and nxt and cout % 8 == 0 and limb[i] and hw % 256 == 0 and hw // 256 <= 64 and
+                 not off("IN_STRIP"))
+        if not nm:
+            continue
+        if in1:
+            out.append("in_fused_x3_kernel<%d>" % (1 if hw <= 64 else 2 if hw <= 128 else 4))
+        elif nxt and cout % 8 == 0:
+            if not strip:
+                out.append("in_stats_kernel")
+            elif x3_ksplit(B * hw, cout, k * k * cin) > 1:  # else the conv's epilogue took them (its unsplit tile)
+                out.append("in_strip_stats_kernel")
+            out += ["in_merge_kernel", "in_apply_f32_kernel" if f32a_layer(i + 1) else "in_apply_x3_kernel"]
+        else:
+            out += ["in_stats_pivot_kernel", "in_apply_kernel"]
+    return out

@@ -332,7 +332,7 @@ def test_encoder_f32a_convs_are_bitwise(gpu_device, monkeypatch, name, B):
 @pytest.mark.parametrize("name,B,hw,nc", [("cifar10", 128, 32, 3), ("cifar10", 200, 32, 3), ("celeba64", 32, 64, 3),
                                          ("mnist", 64, 28, 1)])
 def test_encoder_dense_head_vs_fp64(gpu_device, monkeypatch, name, B, hw, nc):
-    """The last conv as the dense head (encoder.hip enc_head_x3_kernel: the PyTorch weight read as fp32 and split into
+    """The last conv as the dense head (enc_head.hip enc_head_x3_kernel: the PyTorch weight read as fp32 and split into
     limbs in the kernel, one workgroup per 128 rows x 64 columns x 512-k sign block, slabs summed in order) and on the
     limb GEMM over the packed weight limbs (DAMC_ENC_HEAD=0): both against fp64 within 3x the fp32 reference's distance;
     B = 200 has a partial 128-row block, mnist a 3 x 3 head (K = 4608).  The head's two launches appear in a profile
